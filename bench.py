@@ -2,6 +2,8 @@
 """bench.py -- env-steps/s through the PPO-Lagrangian update on MI355X (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W        (N > 1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --dump-outputs DIR               (also writes what the last timed step computed as DIR/<name>.npy)
+  python bench.py ... --full                           (also every secondary measurement and check listed below)
 
 A "step" = ONE full PPO-Lagrangian update over a synthetic rollout already resident in HBM:
   reward+cost GAE  ->  lambda update  ->  update_repeats(4) x [3 towers x (forward, fused loss, backward),
@@ -11,9 +13,12 @@ constraint active (cost_limit 2.31964, lambda moves), 12 goal tokens, all 16 384
 N > 1: the same 64 envs x 256 steps on EVERY GPU (weak scaling; C4 = "256 envs over 8 GPUs" is the 32-envs/GPU point and is
 reported, with C2 and the 64-token probe, under "secondary" at N=1).  `--gpus N` without a torchrun environment re-executes
 itself under torch.distributed.run (one rank per GPU, RCCL) and fails loudly if fewer than N GPUs are visible.
-Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (the bf16 MFMA GEMM, timed with HIP events on
-its launch stream in a separate instrumented update) and a CPU baseline (the fp32 oracle port on the host cores, bounded
-sample).  The oracle is only the checker/baseline leg here -- the measured path is the HIP library.
+Prints ONE JSON line (rank 0).  A plain run only sets up, warms up, times the K steps (and dumps their outputs on request).
+With --full the line also carries the roofline of the dominant kernel (the bf16 MFMA GEMM, timed with HIP events on
+its launch stream in a separate instrumented update), a CPU baseline (the fp32 oracle port on the host cores, bounded
+sample) with the stock PyTorch-ROCm leg and the parity gate, and the secondary configurations (acting path, north-star
+probe, collect-then-update, C4-shard / C2 / C5-shard); the --no-* options switch single legs of --full off.
+The oracle is only the checker/baseline leg here -- the measured path is the HIP library.
 """
 import argparse
 import json
@@ -496,6 +501,27 @@ def timed_updates(eng, st, nxt, ep, steps, warmup, world, dev):
     return dt / steps * 1e3, info, step
 
 
+def dump_outputs(out_dir, eng, st, info, sample=1 << 21):
+    """What the last timed update computed, as a caller of engine.update receives it, written to out_dir/<name>.npy (float32 / float64, ~17 MB):
+    the loss scalars it returns (info_<key>.npy), the returns and advantages of the rollout (GAE), and the flat parameter arena after its Adam
+    step with the (all-reduced) gradient of its last minibatch -- a fixed, seeded sample of `sample` elements where the arena is larger."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    ar, T = eng.model.arena, st.T
+    n = ar.flat_p.numel()
+    idx = None
+    if n > sample:
+        idx = torch.from_numpy(np.unique(np.random.default_rng(0x5AFE).integers(0, n, sample))).to(ar.flat_p.device)
+    pick = (lambda x: x) if idx is None else (lambda x: x.index_select(0, idx))
+    arrays = {"params": pick(ar.flat_p), "grads": pick(ar.flat_g), "returns": st.returns[:T], "c_returns": st.c_returns[:T],
+              "adv_targ": st.adv_targ, "c_adv_targ": st.c_adv_targ}
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v.detach().float().cpu().numpy())
+    for k, v in info.items():
+        np.save(os.path.join(out_dir, f"info_{k}.npy"), np.array([v], dtype=np.float64))
+
+
 def secondary_config(model, dev, name, task, T, B, L, env_chunk, cost_limit, fp8=False, t5_per_row=False):
     """Another BASELINE configuration through the same engine (1 warm-up + 1 timed update; parity-test cases, not the bench line).
     fp8: the fusion-encoder attention on the e4m3 / e5m2 kernels (BASELINE configs[4]: "fp8 MFMA attention"), acting pass included."""
@@ -616,9 +642,14 @@ def main():
     ap.add_argument("--fp8-attention", action="store_true", help="fusion-encoder attention on the e4m3 / e5m2 MFMA kernels in the HEADLINE run (BASELINE configs[4]: "
                     "--gpus 8 --scaling strong --global-envs 256 --task Mixed --L 64 --fp8-attention)")
     ap.add_argument("--t5-dropout-per-row", action="store_true", help="headline run with the reference's train-mode T5 statistics: one dropout realisation per (t, b) row and tower "
-                    "(default: one per unique goal and pass; both figures are in the default line)")
+                    "(default: one per unique goal and pass; --full reports both figures)")
     ap.add_argument("--grad-allreduce-bf16", action="store_true", help="the three per-tower gradient all-reduces cross xGMI as bf16 (126 MB instead of 252 MB per optimiser step)")
+    ap.add_argument("--full", action="store_true", help="also the roofline, the CPU / stock PyTorch-ROCm baselines, the parity gate and the secondary configurations "
+                    "(off by default: a plain run only times the headline update)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed update computed to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.cpu_c1_full:
         print(json.dumps({"cpu_c1_full": cpu_c1_full(not args.eval_mode)}), flush=True)
@@ -675,6 +706,8 @@ def main():
         eng = PPOLagEngine(model, cfg)
         ms, info, step = timed_updates(eng, st, nxt, ep, args.steps, args.warmup, world, dev)
     per_rank_ms = list(timed_updates.per_rank_ms)
+    if rank == 0 and args.dump_outputs:      # before anything below runs another update on the same model
+        dump_outputs(args.dump_outputs, eng, st, info)
     env_steps = T * (args.global_envs if args.scaling == "strong" else B * world)
     S, R = 169 + args.L, T * B
     U = int(st.observations["goal_token_ids"][:T].reshape(R, -1).unique(dim=0).shape[0])
@@ -683,7 +716,7 @@ def main():
     roof = None
     gt = None
     parity_failed = False
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # one extra, instrumented update: EVERY rank runs it (it contains the gradient / cost all-reduces), rank 0 times its
         # MFMA-kernel launches with HIP events
         if rank == 0:
@@ -760,7 +793,7 @@ def main():
     ns = None
     loop = None
     secondary = None
-    if rank == 0 and world == 1 and not args.no_secondary:
+    if rank == 0 and world == 1 and args.full and not args.no_secondary:
         # secondary measurements must never take the headline line down: each one is guarded on its own
         def guarded(fn, *a):
             try:
@@ -783,7 +816,7 @@ def main():
                      guarded(secondary_config, model, dev, "C5-shard fp8: the same with the fusion-encoder attention on fp8 MFMA (BASELINE configs[4])", "Mixed", 256, 32, 64, None, 2.31964, True),
                      guarded(secondary_config, model, dev, "C3 with the reference-faithful T5 dropout (the headline workload, t5_dropout_per_row=True)", "PickUp", 256, 64, 12, None, 2.31964, False, True)]
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(L=args.L, train_mode=not args.eval_mode)
             one = cpu_baseline(T=8, B=2, L=args.L, train_mode=not args.eval_mode, threads=1)     # also at n = 1

@@ -209,5 +209,29 @@ def main_siglip(tc, ef):
     print("wrote g9_il_siglip.npz: loss", out["loss"].item(), "trained tensors", len(names))
 
 
+def main_presets():
+    """tests/golden/il_presets.json: the reference's preset table (early_fusion_tsfm_models.py:221-312, ``build_model``) as data -- per preset name the
+    image encoder, the text encoder, (layers, width, heads) of the fusion transformer (null where the preset has none) and of the decoder."""
+    import json
+    import re
+
+    src = open(os.path.join(REF, "architecture", "models", "transformer_models", "early_fusion_tsfm_models.py")).read()
+    src = src[src.index("def build_model"):src.index("model = EarlyFusionCnnTransformer(model_cfg)")]
+    seen = {}
+    for blk in re.split(r"\n\s+(?:if|elif) model_version == ", src)[1:]:
+        names = re.findall(r'"([a-zA-Z0-9_]+)"', blk.split(":")[0])
+        img = re.search(r'image_encoder = "(\w+)"', blk).group(1)
+        txt = re.search(r'text_encoder = "([\w-]+)"', blk).group(1)
+        fus = re.search(r"fusion_xformer = TransformerConfig\((\d+), (\d+), (\d+)\)", blk)
+        dec = re.search(r"model_cfg.decoder = TransformerConfig\((\d+), (\d+), (\d+)\)", blk)
+        for n in names:
+            seen[n] = {"image_encoder": img, "text_encoder": txt, "fusion": [int(v) for v in fus.groups()] if fus else None,
+                       "decoder": [int(v) for v in dec.groups()]}
+    with open(os.path.join(HERE, "il_presets.json"), "w") as f:       # one preset per line
+        f.write("{\n" + ",\n".join(f" {json.dumps(n)}: {json.dumps(seen[n], sort_keys=True)}" for n in sorted(seen)) + "\n}\n")
+    print("wrote il_presets.json:", len(seen), "presets")
+
+
 if __name__ == "__main__":
     main()
+    main_presets()

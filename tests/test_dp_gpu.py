@@ -70,7 +70,7 @@ def test_bench_two_ranks_well_formed_line(scaling):
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--T", "8",
-           "--envs-per-gpu", "4", "--no-cpu-baseline", "--no-secondary", "--scaling", scaling, "--global-envs", "7"]
+           "--envs-per-gpu", "4", "--full", "--no-cpu-baseline", "--no-secondary", "--scaling", scaling, "--global-envs", "7"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -168,3 +168,36 @@ def test_bench_single_rank_through_rccl():
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["rccl_ranks"] == 1 and out["collective_preflight"]["backend"] == "nccl"
     assert out["collective_preflight"]["tower_ranges_checked"] == 3 and out["loss"]["env_steps"] == 32 and out["value"] > 0
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain bench run (no --full) prints the headline line without any of the --full legs, and --dump-outputs writes what its last timed update
+    computed (float32 / float64, at most 64 MB); two runs with the same arguments (deterministic accumulation) write the same arrays."""
+    import json
+
+    import numpy as np
+
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--T", "8", "--envs-per-gpu", "4",
+               "--deterministic", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        runs.append((line, {f.name[:-4]: np.load(f) for f in d.glob("*.npy")}))
+    line, a = runs[0]
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    assert line["unit"] == "env-steps/s" and abs(line["value"] - 32 / (line["ms_per_step"] * 1e-3)) < 1e-2 * line["value"]
+    assert all(line[k] is None for k in ("roofline", "cpu_baseline", "acting", "collect_then_update", "north_star_batch256", "secondary"))
+    assert "parity_ok" not in line
+    assert {"params", "grads", "returns", "c_returns", "adv_targ", "c_adv_targ", "info_ppo_total", "info_lagrangian_multiplier", "info_env_steps"} <= set(a)
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in a.values())
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["returns"].shape == (8, 4, 1) and a["info_env_steps"][0] == 32 and a["params"].shape == a["grads"].shape and (a["grads"] != 0).any()
+    b = runs[1][1]
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert np.array_equal(a[k], b[k]) if not k.startswith("info_") else np.allclose(a[k], b[k], rtol=1e-6, atol=1e-9), k
