@@ -142,7 +142,9 @@ int svla_gemm_f32(const float* A, long sam, long sak, const float* B, long sbn, 
 int svla_colsum_f32(const float* X, long ldx, int M, int N, int row_stride, float* out, void* stream);
 
 /* ---- attention ---------------------------------------------------------------------------------------------- */
-/* softmax(scale * Q K^T [+ bias] [mask]) V per (row, head), head_dim 64, tokens of one row contiguous (row*S + s).
+/* softmax(scale * Q K^T [+ bias] [mask]) V per (row, head), head_dim 64 or 96, tokens of one row contiguous (row*S + s).
+ * head_dim 96 (TransformerConfig(n, 768, 8): base_6, siglip_base_3_6; csrc/attn_hd96.hip): S <= 256, forward and backward, mask_mode 0 / 1, kvalid, Sq / ldq / lddq,
+ * kv_rows, dropout and D_ws as below; no bias (T5 heads are 64 wide) and no S > 256: those return SVLA_EINVAL, as does any other head_dim.
  * mask_mode 0: none (nn.MultiheadAttention in the fusion encoder, allenact_dino_transformer.py:545-552,702-708);
  * 1: block-causal on traj ids (allenact_dino_transformer.py:398-402 + llama/model.py:317-319).
  * bias [H,S,S] + kvalid [rows,S]: T5 self-attention.  LSE [rows,H,Sq] is saved for the backward.

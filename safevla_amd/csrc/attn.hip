@@ -11,6 +11,7 @@
 // lane-local (+2 cross-lane steps), and the probabilities already sit in the MFMA A-operand layout of P.V;
 // V (and K/Q/dO in the backward) are read as B operands straight from row-major LDS with ds_read_b64_tr_b16.
 #include "common.h"
+#include "attn_hd96.h"      // head_dim 96: its own kernels and LDS layout (attn_hd96.hip)
 
 #ifndef ATT_SWZ_OLD
 #define ATT_SWZ_OLD 0
@@ -1380,6 +1381,7 @@ extern "C" int svla_attn_fwd_bf16(const bf16_t* Q, const bf16_t* K, const bf16_t
                                   int rows, int S, int H, int head_dim, float scale, int mask_mode, const int* traj,
                                   const float* bias, const unsigned char* kvalid, int Sq, long ldq, int kv_rows, const svla_dropout* drop,
                                   void* stream) {
+    if (head_dim == 96) return attn96_fwd_launch(Q, K, V, ld, O, ldo, LSE, rows, S, H, scale, mask_mode, traj, bias, kvalid, Sq, ldq, kv_rows, drop, stream);
     if (head_dim != HD || rows <= 0 || S <= 0 || S > 512 || (ld % 8) || H <= 0 || (kv_rows > 0 && kv_rows < S)) return SVLA_EINVAL;
     if (mask_mode == MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
     if (Sq < 0 || Sq > S || (Sq > 0 && (ldq % 8))) return SVLA_EINVAL;
@@ -1409,6 +1411,8 @@ extern "C" int svla_attn_bwd_bf16(const bf16_t* Q, const bf16_t* K, const bf16_t
                                   int rows, int S, int H, int head_dim, float scale, int mask_mode, const int* traj,
                                   const float* bias, const unsigned char* kvalid, int Sq, long ldq, long lddq, float* D_ws,
                                   const svla_dropout* drop, void* stream) {
+    if (head_dim == 96)
+        return attn96_bwd_launch(Q, K, V, ld, O, ldo, LSE, dO, lddo, dQ, dK, dV, ldd, rows, S, H, scale, mask_mode, traj, bias, kvalid, Sq, ldq, lddq, D_ws, drop, stream);
     if (head_dim != HD || rows <= 0 || S <= 0 || S > 256 || (ld % 8) || (lddo % 8) || H <= 0) return SVLA_EINVAL;
     if (mask_mode == MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
     if (Sq < 0 || Sq > S || (Sq > 0 && ((ldq % 8) || (lddq % 8)))) return SVLA_EINVAL;

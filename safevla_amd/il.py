@@ -1,6 +1,6 @@
 """Offline imitation-learning workload on the same kernels.
 
-Mirrors ``EarlyFusionCnnTransformer`` with the llama decoder, in every ``model_version`` the reference can construct (512 x 8 and 768 x 12 on the MFMA attention kernels; 768 x 8 = heads of 96 on the fp32 ones)
+Mirrors ``EarlyFusionCnnTransformer`` with the llama decoder, in every ``model_version`` the reference can construct (512 x 8 and 768 x 12 on the 64-wide MFMA attention kernels; 768 x 8 = heads of 96 on the 96-wide ones, csrc/attn_hd96.hip)
 (/root/reference/architecture/models/transformer_models/early_fusion_tsfm_models.py:49-207,221-312; ``VERSIONS`` below): text-conditioned multi-camera
 encoder (text_cond_visual_encoder.py:56-268) -> + last-action / in-hand / time embeddings (:120-157) -> causal llama decoder ->
 ``actor`` -> ``nn.CrossEntropyLoss(ignore_index=-1)`` (:93,115-117); and the optimiser of ``training/offline/train_pl.py:283-287``
@@ -50,7 +50,7 @@ class EarlyFusionCnnTransformer(Tower):
     # fusion transformer and decoder are TransformerConfig(n, 512, 8), with the llama decoder (``use_llama_decoder`` defaults to True, :46):
     # DINOv2-S / -B, SigLIP-B / -L (image trunk + text tower) and CLIP RN50 (pre-encoded features only: its conv trunk is not built).
     # and the 768-wide presets whose heads are 64 wide (12 heads: siglip_base_6_3 / _6_6 / _12_12; same kernels at D = 768, llama hidden 2048).
-    # TransformerConfig(n, 768, 8) = heads of 96 (base_6, and the fusion transformer of siglip_base_3_6) builds too, with its attention on the fp32 kernels.
+    # TransformerConfig(n, 768, 8) = heads of 96 (base_6, and the fusion transformer of siglip_base_3_6) builds too, with its attention on the 96-wide MFMA kernels (csrc/attn_hd96.hip).
     # Four more names cannot be constructed in the reference as shipped: small_3_nonTxEnc / siglip_base_3_nonTxEnc (``globals()["NonTxMultiCameraVisualEncoder"]``, :64, is a KeyError: the class is not
     # imported into that module, :22-28) and siglip_base_384_3 / siglip_base_384_resize_3 (image encoders absent from IMAGE_ENCODERS, image_encoders.py:103-112).
     VERSIONS = {"small": (3, 3, 384, "t5-small"), "small_3": (3, 3, 384, "t5-small"), "small_6": (6, 6, 384, "t5-small"), "base_3": (3, 3, 768, "t5-small"),
@@ -58,7 +58,7 @@ class EarlyFusionCnnTransformer(Tower):
                 "siglip_base_6": (6, 6, 768, "SigLIPBase"), "siglip_large_3": (3, 3, 1024, "SigLIPLarge"), "clip_resnet_50_3": (3, 3, 2048, "t5-small"),
                 "siglip_base_6_3": (6, 3, 768, "SigLIPBase", 768, 12), "siglip_base_6_6": (6, 6, 768, "SigLIPBase", 768, 12),
                 "siglip_base_12_12": (12, 12, 768, "SigLIPBase", 768, 12),
-                # heads of 96 (768 / 8): attention on the fp32 kernels (ops.attn_fwd head_dim != 64), everything else as above -- a slow path
+                # heads of 96 (768 / 8): attention on the 96-wide MFMA kernels (ops.attn_fwd head_dim = 96; SVLA_ATTN96_F32=1: the fp32 detour), everything else as above
                 "base_6": (6, 6, 768, "t5-small", 768, 8), "siglip_base_3_6": (3, 6, 768, "SigLIPBase", 768, 8, 12)}
 
     def __init__(self, device="cuda", max_length: int = 1000, input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"),

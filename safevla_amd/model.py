@@ -140,8 +140,8 @@ class Tower(nn.Module):
         D = self.D = d_model
         H = self.H = n_heads                      # fusion transformer (nn.TransformerEncoderLayer nhead)
         self.Hdec = n_heads_decoder               # llama decoder (ModelArgs.n_heads); TransformerConfig(3, 768, 8) + TransformerConfig(6, 768, 12) = siglip_base_3_6
-        # head widths: 64 everywhere on the MFMA attention kernels; any other width (96 = 768 / 8: base_6, siglip_base_3_6) takes the fp32 attention kernels
-        # through fp32 copies of the operands (ops.attn_fwd: a slow path)
+        # head widths: 64 and 96 (= 768 / 8: base_6, siglip_base_3_6) on the MFMA attention kernels (csrc/attn.hip, csrc/attn_hd96.hip); any other width takes the
+        # fp32 attention kernels through fp32 copies of the operands (ops.attn_fwd: a slow path)
         self.hdim, self.hdim_dec = d_model // n_heads, d_model // n_heads_decoder
         HD = self.dec_hidden = 256 * ((int(2 * 4 * d_model / 3) + 255) // 256)
         self.dino_dim = dino_dim          # channel width of the frozen image features: 384 (ViT-S/14), 768 (ViT-B/14, SigLIP-B), 1024 (ViT-L), 2048 (CLIP RN50)

@@ -1,6 +1,7 @@
 """Stream-aware Python bindings of the C-ABI kernels (include/svla.h).  torch is plumbing only: device memory
 and the current HIP stream.  Every function launches on ``torch.cuda.current_stream()`` and raises on failure."""
 import ctypes
+import os
 import struct
 from typing import Optional, Tuple
 
@@ -427,16 +428,24 @@ def _f32_cols(t, W):
     return t[:, :W].float().contiguous()
 
 
+def _attn96_on_mfma(S, bias) -> bool:
+    """bf16 operands with heads of 96: True = the MFMA kernels of csrc/attn_hd96.hip (S <= 256, no T5 bias), False = the fp32 detour.
+    ``SVLA_ATTN96_F32=1`` (read at every call) forces the detour: the A/B switch of tools/ab_attn96.py and of the routing tests."""
+    return S <= 256 and bias is None and os.environ.get("SVLA_ATTN96_F32", "0") != "1"
+
+
 def attn_fwd(q, k, v, ld, rows, S, H, scale, out=None, ldo=None, mask_mode=MASK_NONE, traj=None, bias=None, kvalid=None,
              save_lse=True, Sq=0, ldq=0, kv_rows=0, drop=None, head_dim=64):
-    """q/k/v: bf16 views whose element (token, h*64+d) sits at token*ld + h*64 + d.  Sq > 0: only the first Sq queries of
+    """q/k/v: bf16 views whose element (token, h*head_dim+d) sits at token*ld + h*head_dim + d.  Sq > 0: only the first Sq queries of
     every row (q then holds Sq rows per batch row with row stride ldq).
 
-    ``head_dim`` != 64 (the two imitation-learning presets with TransformerConfig(n, 768, 8): heads of 96): the MFMA kernels are built for 64-wide heads;
-    those presets take the fp32 attention kernels (same masks, same dropout counters) through fp32 copies of the operands -- a slow path, not a tuned one."""
+    ``head_dim`` 96 (the two imitation-learning presets with TransformerConfig(n, 768, 8)): bf16 operands go to the same bf16 entry points, which run the
+    96-wide MFMA kernels of csrc/attn_hd96.hip -- no mask, ``Sq`` subsets, block-causal ``traj``, ``kvalid``, dropout, ``kv_rows``, S <= 256.  What those kernels do
+    not cover (S > 256, the T5 ``bias``) takes the fp32 attention kernels (same masks, same dropout counters) through fp32 copies of the operands: a slow path,
+    not a tuned one.  The environment variable ``SVLA_ATTN96_F32=1``, read at call time, sends every 96-wide bf16 call down that detour (A/B, tests)."""
     nq = Sq if Sq > 0 else S
     W = H * head_dim
-    if head_dim != 64 and q.dtype != F32:
+    if head_dim != 64 and q.dtype != F32 and not (head_dim == 96 and _attn96_on_mfma(S, bias)):
         q32, k32, v32 = _f32_cols(q, W), _f32_cols(k, W), _f32_cols(v, W)
         o32, lse = attn_fwd(q32, k32, v32, W, rows, S, H, scale, mask_mode=mask_mode, traj=traj, bias=bias, kvalid=kvalid, save_lse=save_lse, Sq=Sq,
                             ldq=W if Sq > 0 else 0, kv_rows=kv_rows, drop=drop, head_dim=head_dim)
@@ -455,7 +464,7 @@ def attn_fwd(q, k, v, ld, rows, S, H, scale, out=None, ldo=None, mask_mode=MASK_
 
 def attn_bwd(q, k, v, ld, o, ldo, lse, do, lddo, dq, dk, dv, ldd, rows, S, H, scale, mask_mode=MASK_NONE, traj=None,
              bias=None, kvalid=None, Sq=0, ldq=0, lddq=0, d_ws=None, drop=None, head_dim=64):
-    if head_dim != 64 and q.dtype != F32:       # heads of 96: fp32 kernels through fp32 copies (see attn_fwd)
+    if head_dim != 64 and q.dtype != F32 and not (head_dim == 96 and _attn96_on_mfma(S, bias)):       # fp32 kernels through fp32 copies (see attn_fwd)
         W = H * head_dim
         q32, k32, v32, o32, do32 = (_f32_cols(t, W) for t in (q, k, v, o, do))
         dq32, dk32, dv32 = torch.empty_like(q32), torch.empty_like(k32), torch.empty_like(v32)
@@ -470,7 +479,7 @@ def attn_bwd(q, k, v, ld, o, ldo, lse, do, lddo, dq, dk, dv, ldd, rows, S, H, sc
     if d_ws is None:   # [rows, H, Sq] fp32 workspace: rowsum(dO * O), handed from the dQ kernel to the dK/dV kernel
         d_ws = torch.empty(rows * H * (Sq or S), device=q.device, dtype=F32)
     lib().call("svla_attn_bwd_bf16", _p(q), _p(k), _p(v), ld, _p(o), ldo, _p(lse), _p(do), lddo, _p(dq), _p(dk), _p(dv), ldd,
-               rows, S, H, 64, float(scale), mask_mode, _p(traj), _p(bias), _p(kvalid), int(Sq), int(ldq), int(lddq), _p(d_ws), _d(drop), _stream())
+               rows, S, H, int(head_dim), float(scale), mask_mode, _p(traj), _p(bias), _p(kvalid), int(Sq), int(ldq), int(lddq), _p(d_ws), _d(drop), _stream())
 
 
 # ---- deterministic gradient accumulation ---------------------------------------------------------------------------------------
