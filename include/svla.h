@@ -145,6 +145,10 @@ int svla_colsum_f32(const float* X, long ldx, int M, int N, int row_stride, floa
 /* softmax(scale * Q K^T [+ bias] [mask]) V per (row, head), head_dim 64 or 96, tokens of one row contiguous (row*S + s).
  * head_dim 96 (TransformerConfig(n, 768, 8): base_6, siglip_base_3_6; csrc/attn_hd96.hip): S <= 256, forward and backward, mask_mode 0 / 1, kvalid, Sq / ldq / lddq,
  * kv_rows, dropout and D_ws as below; no bias (T5 heads are 64 wide) and no S > 256: those return SVLA_EINVAL, as does any other head_dim.
+ * head_dim 64: S <= 512, forward and backward.  Above 256 keys the backward runs the eight-wave kernel pair of csrc/attn_long.hip (a rollout or a whole episode on
+ * the llama decoder's time axis): mask_mode 0 / 1, kvalid, Sq / ldq / lddq, dropout with the forward's counters; D_ws is accepted and not used; dQ / dK / dV are
+ * written by plain stores (bitwise repeatable).  Refused with SVLA_EINVAL, nothing launched: S > 512 (forward and backward), bias with S > 256 in the backward (the
+ * only biased attention, the frozen T5, has no backward).
  * mask_mode 0: none (nn.MultiheadAttention in the fusion encoder, allenact_dino_transformer.py:545-552,702-708);
  * 1: block-causal on traj ids (allenact_dino_transformer.py:398-402 + llama/model.py:317-319).
  * bias [H,S,S] + kvalid [rows,S]: T5 self-attention.  LSE [rows,H,Sq] is saved for the backward.

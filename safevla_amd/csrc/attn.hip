@@ -12,6 +12,7 @@
 // V (and K/Q/dO in the backward) are read as B operands straight from row-major LDS with ds_read_b64_tr_b16.
 #include "common.h"
 #include "attn_hd96.h"      // head_dim 96: its own kernels and LDS layout (attn_hd96.hip)
+#include "attn_long.h"      // backward for 256 < S <= 512: eight-wave kernels with runtime tile loops (attn_long.hip)
 
 #ifndef ATT_SWZ_OLD
 #define ATT_SWZ_OLD 0
@@ -1413,6 +1414,8 @@ extern "C" int svla_attn_bwd_bf16(const bf16_t* Q, const bf16_t* K, const bf16_t
                                   const svla_dropout* drop, void* stream) {
     if (head_dim == 96)
         return attn96_bwd_launch(Q, K, V, ld, O, ldo, LSE, dO, lddo, dQ, dK, dV, ldd, rows, S, H, scale, mask_mode, traj, bias, kvalid, Sq, ldq, lddq, D_ws, drop, stream);
+    if (head_dim == HD && S > 256)      // 256 < S <= 512 (no bias): csrc/attn_long.hip; refuses S > 512 and the T5 bias itself
+        return attn_long_bwd_launch(Q, K, V, ld, O, ldo, LSE, dO, lddo, dQ, dK, dV, ldd, rows, S, H, scale, mask_mode, traj, bias, kvalid, Sq, ldq, lddq, D_ws, drop, stream);
     if (head_dim != HD || rows <= 0 || S <= 0 || S > 256 || (ld % 8) || (lddo % 8) || H <= 0) return SVLA_EINVAL;
     if (mask_mode == MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
     if (Sq < 0 || Sq > S || (Sq > 0 && ((ldq % 8) || (lddq % 8)))) return SVLA_EINVAL;

@@ -464,6 +464,11 @@ def attn_fwd(q, k, v, ld, rows, S, H, scale, out=None, ldo=None, mask_mode=MASK_
 
 def attn_bwd(q, k, v, ld, o, ldo, lse, do, lddo, dq, dk, dv, ldd, rows, S, H, scale, mask_mode=MASK_NONE, traj=None,
              bias=None, kvalid=None, Sq=0, ldq=0, lddq=0, d_ws=None, drop=None, head_dim=64):
+    """Gradients of ``attn_fwd`` (same layout arguments; ``lse`` as the forward saved it, ``drop`` the forward's own ``Dropout``), written to dq / dk / dv.
+
+    bf16 operands with ``head_dim`` 64: S <= 256 runs the kernels of csrc/attn.hip, 256 < S <= 512 (a rollout or an episode longer than 256 steps on the decoder's
+    time axis) the eight-wave pair of csrc/attn_long.hip -- no mask, block-causal ``traj``, ``kvalid``, ``Sq`` subsets, dropout; ``d_ws`` is accepted and not used
+    there.  ``bias`` with S > 256 and S > 512 raise ``SvlaError`` (invalid argument).  Heads of 96 keep their own range (S <= 256 on MFMA, see ``attn_fwd``)."""
     if head_dim != 64 and q.dtype != F32 and not (head_dim == 96 and _attn96_on_mfma(S, bias)):       # fp32 kernels through fp32 copies (see attn_fwd)
         W = H * head_dim
         q32, k32, v32, o32, do32 = (_f32_cols(t, W) for t in (q, k, v, o, do))
