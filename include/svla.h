@@ -147,8 +147,12 @@ int svla_colsum_f32(const float* X, long ldx, int M, int N, int row_stride, floa
  * kv_rows, dropout and D_ws as below; no bias (T5 heads are 64 wide) and no S > 256: those return SVLA_EINVAL, as does any other head_dim.
  * head_dim 64: S <= 512, forward and backward.  Above 256 keys the backward runs the eight-wave kernel pair of csrc/attn_long.hip (a rollout or a whole episode on
  * the llama decoder's time axis): mask_mode 0 / 1, kvalid, Sq / ldq / lddq, dropout with the forward's counters; D_ws is accepted and not used; dQ / dK / dV are
- * written by plain stores (bitwise repeatable).  Refused with SVLA_EINVAL, nothing launched: S > 512 (forward and backward), bias with S > 256 in the backward (the
- * only biased attention, the frozen T5, has no backward).
+ * written by plain stores (bitwise repeatable).  Refused with SVLA_EINVAL, nothing launched: S > 512 (forward and backward, but see the next paragraph), bias with
+ * S > 256 in the backward (the only biased attention, the frozen T5, has no backward).
+ * head_dim 64, forward, 512 < S <= 1024: the single-query ("decode") form only -- Sq == 1, no bias, mask_mode 0, no dropout; kvalid [rows,S] or null, kv_rows >= S,
+ * ldq, optional LSE [rows,H] (natural log) -- on csrc/attn_decode_long.hip: the KV-cached acting step of the llama decoder over a cache window of up to 1024 slots
+ * (the reference's policies and llama caches are built for 1000 steps, its online evaluation runs episodes of 600 and 1000).  Only valid keys are read; a row without
+ * a valid key yields zeros; the cost follows the number of 32-key blocks that hold a valid key, not S.  Every other form above 512 keys, and S > 1024, is SVLA_EINVAL.
  * mask_mode 0: none (nn.MultiheadAttention in the fusion encoder, allenact_dino_transformer.py:545-552,702-708);
  * 1: block-causal on traj ids (allenact_dino_transformer.py:398-402 + llama/model.py:317-319).
  * bias [H,S,S] + kvalid [rows,S]: T5 self-attention.  LSE [rows,H,Sq] is saved for the backward.
@@ -345,7 +349,9 @@ int svla_norm_bwd_f32(const float* dy, int dyG, int dyGS, int dyOFF, const float
                       const float* dres, float* dx, int dxG, int dxGS, int dxOFF, float* dgamma, float* dbeta, float* dtok, float* dx_drop,
                       const svla_dropout* drop, void* stream);
 /* fp32 attention: head_dim <= 128 (64 for the policy; 96 for the imitation-learning presets with TransformerConfig(n, 768, 8), early_fusion_tsfm_models.py:236-240,275-279,
- * whose bf16 activations take these kernels through fp32 copies: the MFMA kernels above are built for 64-wide heads), S <= 512. */
+ * whose bf16 activations take these kernels through fp32 copies: the MFMA kernels above are built for 64-wide heads), S <= 512.  The forward also takes the
+ * single-query form of svla_attn_fwd_bf16 for 512 < S <= 1024 (Sq == 1, head_dim 64, no bias, mask_mode 0, no dropout; kvalid, kv_rows, ldq, LSE as there), so the
+ * verification mode acts through the same cache window; everything else above 512 keys is SVLA_EINVAL. */
 int svla_attn_fwd_f32(const float* Q, const float* K, const float* V, long ld, float* O, long ldo, float* LSE, int rows, int S, int H,
                       int head_dim, float scale, int mask_mode, const int* traj, const float* bias, const unsigned char* kvalid, int Sq,
                       long ldq, int kv_rows, const svla_dropout* drop, void* stream);

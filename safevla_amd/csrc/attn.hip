@@ -13,6 +13,7 @@
 #include "common.h"
 #include "attn_hd96.h"      // head_dim 96: its own kernels and LDS layout (attn_hd96.hip)
 #include "attn_long.h"      // backward for 256 < S <= 512: eight-wave kernels with runtime tile loops (attn_long.hip)
+#include "attn_decode_long.h"      // single-query forward for 512 < S <= 1024 (attn_decode_long.hip)
 
 #ifndef ATT_SWZ_OLD
 #define ATT_SWZ_OLD 0
@@ -1383,6 +1384,11 @@ extern "C" int svla_attn_fwd_bf16(const bf16_t* Q, const bf16_t* K, const bf16_t
                                   const float* bias, const unsigned char* kvalid, int Sq, long ldq, int kv_rows, const svla_dropout* drop,
                                   void* stream) {
     if (head_dim == 96) return attn96_fwd_launch(Q, K, V, ld, O, ldo, LSE, rows, S, H, scale, mask_mode, traj, bias, kvalid, Sq, ldq, kv_rows, drop, stream);
+    if (head_dim == HD && S > 512) {
+        // a cache window of up to 1024 slots exists for the single-query form only (csrc/attn_decode_long.hip: episodes of up to 1000 steps); every other form ends at 512
+        if (Sq != 1 || bias || mask_mode != MASK_NONE || drop_cfg(drop).thr || g_attn_no_decode) return SVLA_EINVAL;
+        return attn_decode_long_launch(Q, K, V, ld, O, ldo, LSE, rows, S, H, scale, kvalid, ldq, kv_rows > 0 ? kv_rows : S, stream);
+    }
     if (head_dim != HD || rows <= 0 || S <= 0 || S > 512 || (ld % 8) || H <= 0 || (kv_rows > 0 && kv_rows < S)) return SVLA_EINVAL;
     if (mask_mode == MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
     if (Sq < 0 || Sq > S || (Sq > 0 && (ldq % 8))) return SVLA_EINVAL;

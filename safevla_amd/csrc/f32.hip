@@ -202,6 +202,57 @@ __global__ void __launch_bounds__(256) attn_fwd_f32_kernel(AttnF32Args p) {
     }
 }
 
+// Single-query forward over a KV-cache window of AF_MAXS < S <= AF_DEC_MAXS keys (the fp32 twin of csrc/attn_decode_long.hip: Sq == 1, 64-wide heads, no bias /
+// trajectory mask / dropout): the whole workgroup works on the one query of its (row, head) -- thread t scores keys t, t + 256, ..., then wave w sums P.V over keys
+// w, w + 4, ....  Masked keys are not read.  Same definitions as attn_fwd_f32_kernel (softmax in fp32, LSE = -inf and a zero row when no key is valid).
+#define AF_DEC_MAXS 1024
+__global__ void __launch_bounds__(256) attn_decode_f32_kernel(AttnF32Args p) {
+    __shared__ float ps[AF_DEC_MAXS];
+    __shared__ float qs[64];
+    __shared__ float red[2][4];
+    __shared__ float os[4][64];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int r = blockIdx.x / p.H, h = blockIdx.x % p.H;
+    const float* Kb = p.K + (size_t)r * p.kv_rows * p.ld + h * 64;
+    const float* Vb = p.V + (size_t)r * p.kv_rows * p.ld + h * 64;
+    if (tid < 64) qs[tid] = p.Q[(size_t)r * p.ldq + h * 64 + tid];
+    __syncthreads();
+    float sc[AF_DEC_MAXS / 256], mx = -INFINITY;
+#pragma unroll
+    for (int u = 0; u < AF_DEC_MAXS / 256; ++u) {
+        const int k = tid + 256 * u;
+        sc[u] = k < p.S ? af_score(p, r, h, 0, k, qs, Kb + (size_t)k * p.ld) : -INFINITY;
+        mx = fmaxf(mx, sc[u]);
+    }
+    mx = wave_max(mx);
+    if (lane == 0) red[0][wid] = mx;
+    __syncthreads();
+    mx = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    float se = 0.f;
+#pragma unroll
+    for (int u = 0; u < AF_DEC_MAXS / 256; ++u) { sc[u] = (sc[u] == -INFINITY) ? 0.f : expf(sc[u] - mx); se += sc[u]; }
+    se = wave_sum(se);
+    if (lane == 0) red[1][wid] = se;
+    __syncthreads();
+    se = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
+    const float inv = se > 0.f ? 1.f / se : 0.f;
+    if (p.LSE && tid == 0) p.LSE[(size_t)r * p.H + h] = se > 0.f ? mx + logf(se) : -INFINITY;
+#pragma unroll
+    for (int u = 0; u < AF_DEC_MAXS / 256; ++u) {
+        const int k = tid + 256 * u;
+        if (k < p.S) ps[k] = sc[u] * inv;
+    }
+    __syncthreads();
+    float o = 0.f;
+    for (int k = wid; k < p.S; k += 4) {
+        const float pk = ps[k];
+        if (pk != 0.f) o = fmaf(pk, Vb[(size_t)k * p.ld + lane], o);
+    }
+    os[wid][lane] = o;
+    __syncthreads();
+    if (tid < 64) p.O[(size_t)r * p.ldo + h * 64 + tid] = (os[0][tid] + os[1][tid]) + (os[2][tid] + os[3][tid]);
+}
+
 // phase 1: dQ per query (and D_q = rowsum(dO * O) into LDS); phase 2: dK / dV per key, recomputing the probabilities
 __global__ void __launch_bounds__(256) attn_bwd_f32_kernel(AttnF32Args p) {
     p.drop = drop_resolve(p.drop);
@@ -291,6 +342,14 @@ __global__ void __launch_bounds__(256) attn_bwd_f32_kernel(AttnF32Args p) {
 extern "C" int svla_attn_fwd_f32(const float* Q, const float* K, const float* V, long ld, float* O, long ldo, float* LSE, int rows, int S,
                                  int H, int head_dim, float scale, int mask_mode, const int* traj, const float* bias,
                                  const unsigned char* kvalid, int Sq, long ldq, int kv_rows, const svla_dropout* drop, void* stream) {
+    if (S > AF_MAXS) {
+        // above AF_MAXS only the single-query form exists, as on the bf16 side (svla_attn_fwd_bf16): 64-wide heads, no bias / trajectory mask / dropout, S <= 1024
+        if (rows <= 0 || S > AF_DEC_MAXS || H <= 0 || head_dim != 64 || Sq != 1 || bias || mask_mode != 0 || drop_cfg(drop).thr || (kv_rows && kv_rows < S)) return SVLA_EINVAL;
+        AttnF32Args pd{Q, K, V, ld, O, ldo, LSE, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, kvalid, S, H, 0, scale,
+                       kv_rows ? kv_rows : S, 1, ldq, 0, drop_cfg(nullptr), 64};
+        hipLaunchKernelGGL(attn_decode_f32_kernel, dim3(rows * H), dim3(256), 0, (hipStream_t)stream, pd);
+        return svla_launch_status();
+    }
     if (rows <= 0 || S <= 0 || S > AF_MAXS || H <= 0 || head_dim <= 0 || head_dim > AF_MAXHD || (mask_mode == 1 && !traj) || Sq < 0 || Sq > S) return SVLA_EINVAL;
     if (kv_rows && kv_rows < S) return SVLA_EINVAL;
     AttnF32Args p{Q, K, V, ld, O, ldo, LSE, nullptr, 0, nullptr, nullptr, nullptr, 0, traj, bias, kvalid, S, H, mask_mode, scale,

@@ -241,11 +241,13 @@ class EarlyFusionCnnTransformerAgent:
 
     ``goal_spec``: a string (tokenised by ``tokenizer``: for the t5 presets ``text.GoalTokenizer`` -- the real ``t5-small`` vocabulary through its ``spiece_model`` --,
     for the SigLIP presets any callable ``tokenizer([text], context_length=64) -> ids [1, 64]`` like open_clip's; neither vocabulary ships offline) or already
-    tokenised ids (``{"input_ids", "attention_mask"}`` / an id tensor).  ``max_seq_len`` = the KV-cache window: 512 here (the single-query attention kernel's
-    limit; the reference's tasks end at 500 steps, training/online/base.py:129) against the reference's 1000; an episode that outlives it restarts the window (the
-    reference slides it)."""
+    tokenised ids (``{"input_ids", "attention_mask"}`` / an id tensor).  ``max_seq_len`` = the KV-cache window: 1000 by default, the reference's
+    (early_fusion_tsfm_models.py:370; its online evaluation runs episodes of 600 steps, 1000 for RoomVisit / ObjectNavMulti), capped at the 1024 keys of the
+    single-query attention kernels (csrc/attn_decode_long.hip) and at the model's ``max_steps``: every step attends to all steps of the episode so far, as the
+    reference's llama path does.  Only an episode that outlives that window restarts it, with a warning (the reference's llama caches end at 1000
+    steps too)."""
 
-    def __init__(self, model: EarlyFusionCnnTransformer, device="cuda", sampling: str = "greedy", max_seq_len: int = 512, tokenizer=None,
+    def __init__(self, model: EarlyFusionCnnTransformer, device="cuda", sampling: str = "greedy", max_seq_len: int = 1000, tokenizer=None,
                  generator: Optional[torch.Generator] = None):
         from .agent import ALL_STRETCH_ACTIONS
         if sampling not in ("greedy", "sample"):
@@ -255,7 +257,7 @@ class EarlyFusionCnnTransformerAgent:
             # construction, not at the first get_action.  forward(batch) -- training and offline evaluation -- works for these presets.
             raise NotImplementedError(f"the online agent needs 64-wide decoder heads; this preset has heads of {model.hdim_dec} "
                                       "(TransformerConfig(n, 768, 8): base_6, siglip_base_3_6) -- use forward(batch) on whole windows")
-        self.model, self.device, self.sampling, self.max_seq_len = model, torch.device(device), sampling, min(max_seq_len, 512, model.max_steps)
+        self.model, self.device, self.sampling, self.max_seq_len = model, torch.device(device), sampling, min(max_seq_len, 1024, model.max_steps)
         self._warned_window = False
         self.action_list = list(ALL_STRETCH_ACTIONS)
         self.generator = generator

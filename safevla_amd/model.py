@@ -37,6 +37,7 @@ D = 512
 DINO = 384
 NPATCH = 84          # 7 x 12 grid per camera
 TEXT_OFF = 1 + 2 * NPATCH
+MAX_ACTING_WINDOW = 1024          # keys of the single-query attention kernels = longest KV-cache window (max_steps) of the acting step
 TEXT_ENCODER_DIMS = {"t5-small": 512, "SigLIPBase": 768, "SigLIPLarge": 1024}
 BF16, F32 = torch.bfloat16, torch.float32
 import os as _os0
@@ -161,6 +162,10 @@ class Tower(nn.Module):
         self.critic_type = critic_type
         self.arena = arena
         self.device_ = device
+        if not 1 <= int(max_steps) <= MAX_ACTING_WINDOW:
+            # the KV-cache window of the acting step: the single-query attention kernels end at 1024 keys (csrc/attn_decode_long.hip; the reference's policies and
+            # llama caches are built for 1000).  Refused here, not by a kernel status at step 1024 -- or, on the recorded path (S = max_steps), at the first step
+            raise ValueError(f"max_steps = {max_steps}: the KV-cache window of the acting step is limited to {MAX_ACTING_WINDOW} steps")
         self.max_steps = max_steps
         self.time_step_counter = 0
         self.prune_last = True      # dead-output elimination in the last fusion layer (exact; see run_forward)

@@ -439,6 +439,11 @@ def attn_fwd(q, k, v, ld, rows, S, H, scale, out=None, ldo=None, mask_mode=MASK_
     """q/k/v: bf16 views whose element (token, h*head_dim+d) sits at token*ld + h*head_dim + d.  Sq > 0: only the first Sq queries of
     every row (q then holds Sq rows per batch row with row stride ldq).
 
+    Key counts: S <= 512, except the single-query form of the KV-cached acting step -- ``Sq == 1``, ``head_dim`` 64, no ``bias``, no ``traj`` mask, no ``drop`` -- which
+    takes S <= 1024 (bf16: csrc/attn_decode_long.hip; fp32: its twin in csrc/f32.hip): ``kvalid`` [rows, S] or None, ``kv_rows`` >= S, ``ldq``, ``save_lse``.  It reads
+    only the valid keys, so a step costs what its episode's length costs, whatever the window.  Any other form above 512 keys, and S > 1024, raises ``SvlaError``
+    (invalid argument) and launches nothing.
+
     ``head_dim`` 96 (the two imitation-learning presets with TransformerConfig(n, 768, 8)): bf16 operands go to the same bf16 entry points, which run the
     96-wide MFMA kernels of csrc/attn_hd96.hip -- no mask, ``Sq`` subsets, block-causal ``traj``, ``kvalid``, dropout, ``kv_rows``, S <= 256.  What those kernels do
     not cover (S > 256, the T5 ``bias``) takes the fp32 attention kernels (same masks, same dropout counters) through fp32 copies of the operands: a slow path,
