@@ -317,6 +317,30 @@ int svla_vit_tokens(const svla_bf16* patch, const float* cls, const float* pos, 
 int svla_adaptive_pool_tokens(const svla_bf16* x, int B, int skip, int gh, int gw, int C, int oh, int ow, int cam, int ncam,
                               svla_bf16* tok_out, float* chw_out, void* stream);
 
+/* ---- sampled frame augmentation (rollout time, in front of the two entry points above that read raw frames) ------ */
+/* DataAugmentationPreprocessor.process with use_augmentation (architecture/allenact_preprocessors/dino_preprocessors.py:224-231) applies the concrete
+ * transform that utils/transformation_util.py:54-119 samples from the v2 list (utils/transformation_util.py:12-28) to the uint8 frames.  The stages are
+ * u8 [B,H,W,3] -> u8 [B,H,W,3] (x != y, any H >= 5, W >= 3, no alignment of W); every intermediate is rounded to u8 where the op list rounds it.
+ * The ColorJitter operations of a call come in its drawn order: `nops` codes (0 brightness, 1 contrast, 2 saturation, 3 hue), code k in bits 4k..4k+3 of
+ * `ops_packed`, with its factor in f<k>.
+ *
+ * svla_aug_gray_partials: ColorJitter's contrast blends with the mean of the grayscale image (utils/transformation_util.py:15-17,66-79).  Applies the
+ * `nops` operations that precede contrast in the call's order and writes 64 integer partial sums of trunc(0.2989 R + 0.587 G + 0.114 B) per image to
+ * partials[B, 64]; the consumer adds them (integers: exact, order-free, no atomics). */
+int svla_aug_gray_partials(const unsigned char* x, int B, int H, int W, int nops, int ops_packed, float f0, float f1, float f2, float f3,
+                           unsigned long long* partials, void* stream);
+/* ColorJitter (utils/transformation_util.py:66-79: the four operations with fixed factors, order drawn per call) followed by
+ * GaussianBlur(kernel_size=(5, 9)) (utils/transformation_util.py:18,80-87) in one launch: the jittered u8 tile and its halo live in LDS only.
+ * `partials` (from svla_aug_gray_partials) is read when contrast is among the operations.  wx5 / wy9: HOST pointers to the normalised 1-D weights (5 wide,
+ * 9 high; the 2-D kernel is their product; reflect padding); both NULL: no blur, the jittered image is written.  nops == 0: blur only. */
+int svla_aug_jitter_blur_u8(const unsigned char* x, unsigned char* y, int B, int H, int W, int nops, int ops_packed, float f0, float f1, float f2,
+                            float f3, const unsigned long long* partials, const float* wx5, const float* wy9, void* stream);
+/* RandomResizedCrop with the box found on the host (utils/transformation_util.py:19-22,88-96: bilinear, align_corners = False, box -> H x W), the
+ * RandomPosterize entries that the reference rebuilds with bits = 7 (utils/transformation_util.py:98-103: x & 0xFE) and RandomAdjustSharpness(2)
+ * (utils/transformation_util.py:104-109) in one launch.  Box = (0, 0, H, W) is the identity resize.  A box that leaves the image is refused. */
+int svla_aug_resize_post_sharp_u8(const unsigned char* x, unsigned char* y, int B, int H, int W, int top, int left, int bh, int bw, int posterize,
+                                  int sharpen, void* stream);
+
 /* In-place dropout of a [rows, N] bf16 activation, element index row*N + col: the two stand-alone sites of the frozen T5 encoder
  * (after the token embedding, after the final layer norm) that stays in train() mode with the rest of the policy
  * (allenact_dino_transformer.py:193,599-603). */

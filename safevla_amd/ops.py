@@ -710,6 +710,60 @@ def patchify_u8(frames_u8, mean3, std3, out, crop_x=3, P=14, gh=16, gw=27):
                (ctypes.c_float * 3)(*[float(v) for v in std3]), _p(out), _stream())
 
 
+# sampled frame augmentation (csrc/augment.hip): u8 [B,H,W,3] -> u8 [B,H,W,3] stages in front of normalize_u8 / patchify_u8
+AUG_NPART = 64                                                  # integer partial sums per image (csrc/augment.hip: AUG_NPART)
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE = 0, 1, 2, 3      # torchvision ColorJitter's operation codes
+
+
+def _aug_frames(x_u8, name="frames"):
+    _chk(x_u8, torch.uint8, name)
+    if x_u8.dim() != 4 or x_u8.shape[-1] != 3 or not x_u8.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous uint8 [B,H,W,3] tensor, got {tuple(x_u8.shape)}")
+    return x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]
+
+
+def _aug_ops(ops, factors):
+    ops, factors = [int(o) for o in ops], [float(f) for f in factors]
+    assert len(ops) == len(factors) <= 4
+    packed = sum(o << (4 * k) for k, o in enumerate(ops))
+    return len(ops), packed, factors + [0.0] * (4 - len(factors))
+
+
+def aug_gray_partials(x_u8, ops=(), factors=()):
+    """integer partial sums [B, AUG_NPART] of gray(x) per image, x = the frames after the ColorJitter operations ``ops`` (those that precede contrast)"""
+    B, H, W = _aug_frames(x_u8)
+    n, packed, f = _aug_ops(ops, factors)
+    part = torch.empty(B, AUG_NPART, device=x_u8.device, dtype=torch.int64)
+    lib().call("svla_aug_gray_partials", _p(x_u8), B, H, W, n, packed, f[0], f[1], f[2], f[3], _p(part), _stream())
+    return part
+
+
+def aug_jitter_blur(x_u8, ops=(), factors=(), partials=None, wx=None, wy=None, out=None):
+    """the ColorJitter operations ``ops`` (codes AUG_*, in order, with ``factors``) and then, when the 1-D weights wx (5) / wy (9) are given, the 5 x 9 Gaussian
+    blur -- one launch.  ``partials`` (aug_gray_partials of the frames entering contrast) is needed when contrast is among the operations."""
+    B, H, W = _aug_frames(x_u8)
+    n, packed, f = _aug_ops(ops, factors)
+    y = torch.empty_like(x_u8) if out is None else out
+    _aug_frames(y, "out")
+    assert y.shape == x_u8.shape
+    cwx = (ctypes.c_float * 5)(*[float(v) for v in wx]) if wx is not None else None
+    cwy = (ctypes.c_float * 9)(*[float(v) for v in wy]) if wy is not None else None
+    lib().call("svla_aug_jitter_blur_u8", _p(x_u8), _p(y), B, H, W, n, packed, f[0], f[1], f[2], f[3], _p(partials), cwx, cwy, _stream())
+    return y
+
+
+def aug_resize_post_sharp(x_u8, box=None, posterize=False, sharpen=False, out=None):
+    """crop ``box`` = (top, left, height, width) resized to the frame's H x W (None: the whole frame, the identity), then x & 0xFE when ``posterize``, then
+    sharpness factor 2 when ``sharpen`` -- one launch."""
+    B, H, W = _aug_frames(x_u8)
+    top, left, bh, bw = (0, 0, H, W) if box is None else [int(v) for v in box]
+    y = torch.empty_like(x_u8) if out is None else out
+    _aug_frames(y, "out")
+    assert y.shape == x_u8.shape
+    lib().call("svla_aug_resize_post_sharp_u8", _p(x_u8), _p(y), B, H, W, top, left, bh, bw, int(bool(posterize)), int(bool(sharpen)), _stream())
+    return y
+
+
 def vit_tokens(patch, cls, pos, B, NP, C, out):
     lib().call("svla_vit_tokens", _p(patch), _p(cls), _p(pos), B, NP, C, _p(out), _stream())
 

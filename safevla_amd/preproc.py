@@ -2,7 +2,7 @@
 ``process(obs: Dict[str, Tensor]) -> Tensor`` with attributes ``input_uuids`` / ``uuid``:
 
   * ``DataAugmentationPreprocessor``  /root/reference/architecture/allenact_preprocessors/dino_preprocessors.py:166-239
-    (u8 HWC -> /255, -mean, /std; augmentation is a host-configured torchvision op list and is off for synthetic runs)
+    (u8 HWC -> /255, -mean, /std; with use_augmentation the sampled v2 transform of utils/transformation_util.py runs first, as u8 kernels)
   * ``DinoViTPreprocessor`` / ``DinoViTEmbedder``  dino_preprocessors.py:20-125: crop W 384 -> 378, DINOv2 ViT-S/14
     ``forward_features(...)["x_norm_patchtokens"]`` -> (B,384,16,27) -> AdaptiveAvgPool2d((7,12)).
 
@@ -18,8 +18,10 @@ MI355X path: normalise + crop + im2col fused in one kernel, patch embedding and 
 (LayerScale folded into the frozen weights at sync time), fused attention at S = 433, output written directly in the rollout
 storage's bf16 token layout [B, ncam, 84, 384] (and/or the reference's fp32 (B,384,7,12)).
 """
+import functools
 import math
-from typing import Dict, Optional
+import random
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -34,23 +36,188 @@ DINO_RGB_STDS = (0.26862954, 0.26130258, 0.27577711)
 BF16 = torch.bfloat16
 
 
+# ---- sampled frame augmentation: host side (no device needed) -------------------------------------------------------------------
+# The reference samples ONE concrete transform from the v2 list (utils/transformation_util.py:12-28) with Python's ``random`` (sample_a_specific_transform,
+# :54-119), keeps it for num_steps_to_change calls of DataAugmentationPreprocessor.process (dino_preprocessors.py:224-231) and applies it to the whole batch.
+# What torchvision still draws per call with fixed factors -- the order of the four ColorJitter operations and the crop box -- is drawn here per call on a
+# torch generator.  The kernels (csrc/augment.hip) take everything as arguments.
+AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE = ops.AUG_BRIGHTNESS, ops.AUG_CONTRAST, ops.AUG_SATURATION, ops.AUG_HUE
+AUG_STAGES = ("jitter0", "jitter1", "jitter2", "jitter3", "blur", "crop_resize", "posterize", "sharpness")
+
+
+class AugmentParams(NamedTuple):
+    brightness: float
+    saturation: float
+    hue: float
+    contrast: float
+    sigma: float
+    scale: float
+    posterize_draws: Tuple[int, int, int, int]
+    sharpness: int
+
+    @property
+    def posterize(self) -> bool:
+        """every RandomPosterize entry is rebuilt with bits = 7 (transformation_util.py:101-103): clearing the low bit is idempotent, so the four entries
+        reduce to: clear it if any of the four draws is 1"""
+        return any(self.posterize_draws)
+
+    def factor(self, op: int) -> float:
+        return (self.brightness, self.contrast, self.saturation, self.hue)[op]
+
+
+def sample_augment_params(rng=random) -> AugmentParams:
+    """sample_a_specific_transform on the v2 list, in its draw order (ColorJitter: brightness, saturation, hue, contrast; blur sigma; crop scale; four posterize
+    draws; one sharpness draw).  ``rng``: the ``random`` module or a ``random.Random``."""
+    brightness = rng.uniform(0.6, 1.4)          # ColorJitter(brightness=0.4) -> [1 - 0.4, 1 + 0.4]
+    saturation = rng.uniform(0.8, 1.2)
+    hue = rng.uniform(-0.05, 0.05)
+    contrast = rng.uniform(0.6, 1.4)
+    sigma = rng.uniform(0.1, 2)
+    scale = rng.uniform(0.9, 1)
+    post = tuple(int(rng.random() < 0.2) for _ in range(4))
+    sharp = int(rng.random() < 0.5)
+    return AugmentParams(brightness, saturation, hue, contrast, sigma, scale, post, sharp)
+
+
+CROP_RATIO = (3.0 / 4.0, 4.0 / 3.0)
+
+
+def crop_attempts_can_succeed(H: int, W: int, scale: float, ratio=CROP_RATIO) -> bool:
+    """False only when no aspect ratio in ``ratio`` gives a box of area scale * H * W inside H x W (then every attempt of the search fails and the box is the
+    centre-crop fallback: at 224 x 384 the crop height is at least round(sqrt(0.9 * 86016 * 3/4)) = 241 > 224)."""
+    area = H * W * scale
+    r_lo = max(ratio[0], area / (H + 0.5) ** 2)      # h = round(sqrt(area / r)) <= H needs r >= area / (H + 0.5)^2
+    r_hi = min(ratio[1], (W + 0.5) ** 2 / area)      # w = round(sqrt(area * r)) <= W needs r <= (W + 0.5)^2 / area
+    return r_lo <= r_hi * (1 + 1e-6)
+
+
+def crop_box(H: int, W: int, scale: float, generator: Optional[torch.Generator] = None, ratio=CROP_RATIO) -> Tuple[int, int, int, int]:
+    """RandomResizedCrop's parameter search with the scale range collapsed to the sampled value: ten attempts with a log-uniform aspect ratio, then the
+    centre-crop fallback.  Returns (top, left, height, width)."""
+    area = H * W
+    if crop_attempts_can_succeed(H, W, scale, ratio):
+        lo, hi = math.log(ratio[0]), math.log(ratio[1])
+        for _ in range(10):
+            target = area * scale
+            ar = math.exp(torch.empty(1).uniform_(lo, hi, generator=generator).item())
+            w, h = int(round(math.sqrt(target * ar))), int(round(math.sqrt(target / ar)))
+            if 0 < w <= W and 0 < h <= H:
+                top = int(torch.randint(0, H - h + 1, (1,), generator=generator).item())
+                left = int(torch.randint(0, W - w + 1, (1,), generator=generator).item())
+                return top, left, h, w
+    in_ratio = float(W) / float(H)
+    if in_ratio < min(ratio):
+        w = W
+        h = int(round(w / min(ratio)))
+    elif in_ratio > max(ratio):
+        h = H
+        w = int(round(h * max(ratio)))
+    else:
+        w, h = W, H
+    h, w = min(h, H), min(w, W)
+    return (H - h) // 2, (W - w) // 2, h, w
+
+
+@functools.lru_cache(maxsize=64)
+def gaussian_weights(ksize: int, sigma: float) -> Tuple[float, ...]:
+    """normalised 1-D weights exp(-0.5 (x / sigma)^2) on the integer offsets of a ``ksize``-tap kernel, computed in fp32"""
+    half = (ksize - 1) * 0.5
+    x = torch.linspace(-half, half, ksize, dtype=torch.float32)
+    pdf = torch.exp(-0.5 * (x / torch.tensor(sigma, dtype=torch.float32)).pow(2))
+    return tuple((pdf / pdf.sum()).tolist())
+
+
+class AugmentCall(NamedTuple):
+    """everything one call applies: the sampled transform, this call's ColorJitter order and crop box"""
+    params: AugmentParams
+    order: Tuple[int, int, int, int]
+    box: Tuple[int, int, int, int]
+
+
+def apply_augment_u8(x: torch.Tensor, call: AugmentCall, debug: bool = False, out: Optional[torch.Tensor] = None):
+    """u8 [B,H,W,3] -> u8 [B,H,W,3]: ColorJitter in the call's order, blur, crop + resize, posterize, sharpness.
+    Product form: three launches (gray partial sums of the image entering contrast; jitter + blur; resize + posterize + sharpness).
+    ``debug``: every stage in a launch of its own; returns [(stage name, u8 image)] for the eight stages of AUG_STAGES (a stage that was not sampled
+    returns its input)."""
+    p, order = call.params, list(call.order)
+    factors = [p.factor(o) for o in order]
+    wx, wy = gaussian_weights(5, p.sigma), gaussian_weights(9, p.sigma)
+    if not debug:
+        k = order.index(AUG_CONTRAST)
+        part = ops.aug_gray_partials(x, order[:k], factors[:k])
+        y = ops.aug_jitter_blur(x, order, factors, part, wx, wy)
+        return ops.aug_resize_post_sharp(y, call.box, p.posterize, bool(p.sharpness), out=out)
+    stages = []
+    for i, (o, f) in enumerate(zip(order, factors)):
+        part = ops.aug_gray_partials(x) if o == AUG_CONTRAST else None
+        x = ops.aug_jitter_blur(x, [o], [f], part)
+        stages.append((AUG_STAGES[i], x))
+    x = ops.aug_jitter_blur(x, wx=wx, wy=wy)
+    stages.append(("blur", x))
+    x = ops.aug_resize_post_sharp(x, call.box)
+    stages.append(("crop_resize", x))
+    if p.posterize:
+        x = ops.aug_resize_post_sharp(x, posterize=True)
+    stages.append(("posterize", x))
+    if p.sharpness:
+        x = ops.aug_resize_post_sharp(x, sharpen=True)
+    stages.append(("sharpness", x))
+    return stages
+
+
 class DataAugmentationPreprocessor:
+    """dino_preprocessors.py:166-239.  ``use_augmentation=True`` (the reference's default, training/online/dinov2_vits_tsfm_base.py:62,124,152): one transform
+    sampled on the first call and every ``num_steps_to_change`` calls after it, applied to the whole batch as u8 kernels before the normalisation.  Each
+    camera's preprocessor owns its transform.  ``generator``: torch generator of the per-call draws (ColorJitter order, crop box); None = the CPU default."""
+
     def __init__(self, rgb_input_uuid: str, output_uuid: str, device="cuda", normalize=True, mean=DINO_RGB_MEANS, stdev=DINO_RGB_STDS,
-                 height=224, width=384, use_augmentation=False, **kw):
-        if use_augmentation:
-            raise NotImplementedError("torchvision augmentation lists are simulator-side configuration (off for synthetic runs)")
+                 height=224, width=384, use_augmentation=False, num_steps_to_change=500, generator: Optional[torch.Generator] = None, **kw):
         self.input_uuids, self.uuid, self.device = [rgb_input_uuid], output_uuid, torch.device(device)
         self.mean, self.stdev, self.normalize = mean, stdev, normalize
         self.observation_space = Box(-float("inf"), float("inf"), (height, width, 3))        # dino_preprocessors.py:205-214
+        self.use_augmentation = bool(use_augmentation)
+        if self.use_augmentation:
+            assert num_steps_to_change >= 1
+            self.num_steps_to_change, self.num_steps = int(num_steps_to_change), 0
+            self.augmentations: Optional[AugmentParams] = None
+            self.generator = generator
 
     def to(self, device):
         self.device = torch.device(device)
         return self
 
+    def next_call(self, H: int, W: int) -> AugmentCall:
+        """advance the schedule by one call (dino_preprocessors.py:226-228) and draw what this call draws.  Host only."""
+        assert self.use_augmentation, "constructed with use_augmentation=False"
+        if self.num_steps == 0 or self.augmentations is None:
+            self.augmentations = sample_augment_params()
+        self.num_steps = (self.num_steps + 1) % self.num_steps_to_change
+        order = tuple(int(v) for v in torch.randperm(4, generator=self.generator).tolist())
+        return AugmentCall(self.augmentations, order, crop_box(H, W, self.augmentations.scale, self.generator))
+
+    def _frames(self, frames_u8):
+        x = frames_u8.to(self.device)
+        assert x.dtype == torch.uint8 and x.dim() == 4 and x.shape[-1] == 3
+        return x.contiguous()
+
+    def augment_u8(self, frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """u8 [B,H,W,3] -> augmented u8 [B,H,W,3]; counts as one call of the schedule"""
+        x = self._frames(frames_u8)
+        return apply_augment_u8(x, self.next_call(x.shape[1], x.shape[2]), out=out)
+
+    def augment_u8_stages(self, frames_u8: torch.Tensor):
+        """debug form of augment_u8: (AugmentCall, [(stage name, u8 image after that stage)]), one launch per stage; counts as one call of the schedule"""
+        x = self._frames(frames_u8)
+        call = self.next_call(x.shape[1], x.shape[2])
+        return call, apply_augment_u8(x, call, debug=True)
+
     def process(self, obs: Dict[str, torch.Tensor], *a, **k) -> torch.Tensor:
         x = obs[self.input_uuids[0]].to(self.device)
         assert x.dtype == torch.uint8 and x.shape[-1] == 3
-        return ops.normalize_u8(x.contiguous(), self.mean if self.normalize else (0, 0, 0), self.stdev if self.normalize else (1, 1, 1))
+        x = x.contiguous()
+        if self.use_augmentation:
+            x = self.augment_u8(x)
+        return ops.normalize_u8(x, self.mean if self.normalize else (0, 0, 0), self.stdev if self.normalize else (1, 1, 1))
 
 
 # geometry presets: (dim, depth, heads, patch, native_grid, class token, LayerScale)
@@ -180,8 +347,11 @@ class _ViTPreprocessorBase:
     ``process_tokens`` writes the storage-native bf16 tokens [B, ncam, 84, C]."""
     MEAN, STD, CROP_X, HW = DINO_RGB_MEANS, DINO_RGB_STDS, 3, (224, 384)
 
-    def _setup(self, rgb_input_uuid, output_uuid, model_type, device, flatten):
+    def _setup(self, rgb_input_uuid, output_uuid, model_type, device, flatten, augmenter=None):
         self.input_uuids, self.uuid, self.device = [rgb_input_uuid], output_uuid, torch.device(device)
+        # optional frame augmentation in front of the patchify kernel: a DataAugmentationPreprocessor(use_augmentation=True) (anything with ``augment_u8``), or
+        # one per camera (a list) for process_tokens / process_tokens_all_cameras.  None: the frames go to the trunk as they come.
+        self.augmenters = [] if augmenter is None else (list(augmenter) if isinstance(augmenter, (list, tuple)) else [augmenter])
         self.vit = DinoViT(self.device, **VIT_PRESETS[model_type])
         C = self.vit.dim
         self.observation_space = Box(-float("inf"), float("inf"), (7 * 12, C) if flatten else (7, 12, C))
@@ -193,9 +363,16 @@ class _ViTPreprocessorBase:
         assert tuple(fr.shape[1:3]) == self.HW, f"Expected shape is {self.HW[0]}x{self.HW[1]}; got {tuple(fr.shape[1:3])}"
         return self.vit.patch_tokens(fr, self.MEAN, self.STD, crop_x=self.CROP_X)
 
+    def _augment(self, fr, cam: int = 0):
+        if not self.augmenters:
+            return fr
+        assert cam < len(self.augmenters) or len(self.augmenters) == 1, f"camera {cam}: {len(self.augmenters)} augmenters"
+        return self.augmenters[cam if len(self.augmenters) > 1 else 0].augment_u8(fr)
+
     @torch.no_grad()
     def process(self, obs: Dict[str, torch.Tensor], *a, **k) -> torch.Tensor:
-        fr = obs[self.input_uuids[0]].to(self.device)
+        assert len(self.augmenters) <= 1, "process serves one camera: pass one augmenter"
+        fr = self._augment(obs[self.input_uuids[0]].to(self.device))
         x = self._tokens(fr)
         B, v = fr.shape[0], self.vit
         gh, gw = self._rt_grid()
@@ -208,7 +385,7 @@ class _ViTPreprocessorBase:
 
     @torch.no_grad()
     def process_tokens(self, frames_u8: torch.Tensor, out_tokens: torch.Tensor, cam: int, ncam: int = 2):
-        x = self._tokens(frames_u8.to(self.device))
+        x = self._tokens(self._augment(frames_u8.to(self.device), cam))
         gh, gw = self._rt_grid()
         ops.adaptive_pool_tokens(x, frames_u8.shape[0], 1 if self.vit.has_cls else 0, gh, gw, self.vit.dim, 7, 12, cam=cam, ncam=ncam, tok_out=out_tokens)
 
@@ -216,10 +393,18 @@ class _ViTPreprocessorBase:
     @torch.no_grad()
     def process_tokens_all_cameras(self, frames_u8: torch.Tensor, out_tokens: torch.Tensor):
         """frames_u8 [ncam * B, H, W, 3] (camera-major: all envs' frames of camera 0, then camera 1, ...) -> out_tokens [B, ncam, 84, C] in ONE pass of the trunk
-        (the rollout's two cameras share the frozen encoder: one 2B-frame batch fills the GPU better than two B-frame batches)."""
+        (the rollout's two cameras share the frozen encoder: one 2B-frame batch fills the GPU better than two B-frame batches).  With augmenters (one per
+        camera) each camera's slice is augmented by its own augmenter first."""
         B, ncam = out_tokens.shape[0], out_tokens.shape[1]
         assert frames_u8.shape[0] == ncam * B
-        x = self._tokens(frames_u8.to(self.device))
+        fr = frames_u8.to(self.device)
+        if self.augmenters:
+            assert len(self.augmenters) == ncam, f"{ncam} cameras need {ncam} augmenters, got {len(self.augmenters)}"
+            aug = torch.empty_like(fr, memory_format=torch.contiguous_format)
+            for cam, a in enumerate(self.augmenters):
+                a.augment_u8(fr[cam * B:(cam + 1) * B], out=aug[cam * B:(cam + 1) * B])
+            fr = aug
+        x = self._tokens(fr)
         gh, gw = self._rt_grid()
         for cam in range(ncam):
             ops.adaptive_pool_tokens(x[cam * B:(cam + 1) * B], B, 1 if self.vit.has_cls else 0, gh, gw, self.vit.dim, 7, 12, cam=cam, ncam=ncam, tok_out=out_tokens)
@@ -228,11 +413,11 @@ class _ViTPreprocessorBase:
 class DinoViTPreprocessor(_ViTPreprocessorBase):
     """dino_preprocessors.py:38-125: 224 x 384 frames, W crop [3:-3], DINOv2 ``x_norm_patchtokens`` -> (B, C, 16, 27) -> pool (7, 12)."""
 
-    def __init__(self, rgb_input_uuid: str, output_uuid: str, dino_model_type: str = "dinov2_vits14", device="cuda", flatten: bool = True, **kw):
+    def __init__(self, rgb_input_uuid: str, output_uuid: str, dino_model_type: str = "dinov2_vits14", device="cuda", flatten: bool = True, augmenter=None, **kw):
         if dino_model_type == "dinov2_vitg14":
             raise NotImplementedError("dinov2_vitg14 (SwiGLU-fused MLP, 40 blocks) is not built; ViT-S/B/L-14 are")
         assert dino_model_type in ("dinov2_vits14", "dinov2_vitb14", "dinov2_vitl14"), dino_model_type
-        self._setup(rgb_input_uuid, output_uuid, dino_model_type, device, flatten)
+        self._setup(rgb_input_uuid, output_uuid, dino_model_type, device, flatten, augmenter)
 
 
 class SigLIPPreprocessor(_ViTPreprocessorBase):
@@ -242,6 +427,6 @@ class SigLIPPreprocessor(_ViTPreprocessorBase):
     SIGLIP_RGB_MEANS, SIGLIP_RGB_STDS = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
     MEAN, STD, CROP_X, HW = SIGLIP_RGB_MEANS, SIGLIP_RGB_STDS, 0, (256, 256)
 
-    def __init__(self, rgb_input_uuid: str, output_uuid: str, siglip_model_type: str = "ViT-B-16-SigLIP-256", device="cuda", flatten: bool = True, **kw):
+    def __init__(self, rgb_input_uuid: str, output_uuid: str, siglip_model_type: str = "ViT-B-16-SigLIP-256", device="cuda", flatten: bool = True, augmenter=None, **kw):
         assert siglip_model_type in ("ViT-B-16-SigLIP-256", "ViT-L-16-SigLIP-256"), siglip_model_type
-        self._setup(rgb_input_uuid, output_uuid, siglip_model_type, device, flatten)
+        self._setup(rgb_input_uuid, output_uuid, siglip_model_type, device, flatten, augmenter)
