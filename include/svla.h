@@ -341,6 +341,26 @@ int svla_aug_jitter_blur_u8(const unsigned char* x, unsigned char* y, int B, int
 int svla_aug_resize_post_sharp_u8(const unsigned char* x, unsigned char* y, int B, int H, int W, int top, int left, int bh, int bw, int posterize,
                                   int sharpen, void* stream);
 
+/* ---- frozen CLIP RN50 image trunk (clip_resnet_50_3; rollout / data-loading time) ------------------------------------------------
+ * ClipResNet (architecture/models/transformer_models/image_encoders.py:11-48, pool=False -> (2048, 7, 12)) runs CLIP's ModifiedResNet [3P openai/CLIP], layers
+ * (3, 4, 6, 3), width 64, on 224 x 384 frames normalised with the CLIP mean / std (architecture/models/transformer_models/preprocessors.py:27).  Activations are
+ * NHWC bf16 = rows [B*H*W, C]; eval-mode BatchNorm is folded by the caller (weights * gamma / sqrt(var + eps), bias = beta - mean * gamma / sqrt(var + eps)).
+ *
+ * svla_conv_nhwc_bf16: y = epi(conv(x, w) + bias), stride 1, "same" zero padding, taps = 9 (3x3: Bottleneck.conv2 and the stem's conv2 / conv3) or 1 (1x1:
+ * Bottleneck.conv1 / conv3 / downsample.0), as an implicit GEMM on v_mfma_f32_16x16x32_bf16 with fp32 accumulation -- the A operand is gathered per tap from x,
+ * no im2col matrix is written.  x [B,H,W,Cin]; w [Cout, taps, Cin] (tap = ky*3 + kx); bias fp32 [Cout]; Cin % 32 == 0, Cout % 32 == 0; any H, W >= 1.
+ * epi: 0 = + bias, 1 = ReLU(. + bias), 2 = ReLU(. + bias + residual) (the block's output, ReLU(out + identity); residual rows [B*H*W] of stride ldr).
+ * Output pixel m is written at row (yG > 0 ? (m / yG) * yGS + m % yG : m) of stride ldy: yG = 84, yGS = ncam * 84 writes the last block straight into one camera
+ * slot of the token tensor [B, ncam, 84, 2048].  Anything else is SVLA_EINVAL, nothing launched. */
+int svla_conv_nhwc_bf16(const svla_bf16* x, const svla_bf16* w, const float* bias, const svla_bf16* residual, long ldr, svla_bf16* y, long ldy, int yG, long yGS,
+                        int B, int H, int W, int Cin, int Cout, int taps, int epi, void* stream);
+/* The stem's first layer in one pass: u8 [B,H,W,3] -> (x / 255 - mean) / std -> conv1 3 -> 32, 3x3, stride 2, pad 1 (zero padding of the normalised image) -> folded
+ * bn1 -> ReLU -> bf16 [B, ceil(H/2), ceil(W/2), 32].  mean3 / std3: HOST pointers; w fp32 [27][32] on the device, k = (ky*3 + kx)*3 + c; bias fp32 [32]. */
+int svla_conv_stem_u8_bf16(const unsigned char* frames, int B, int H, int W, const float* mean3, const float* std3, const float* w, const float* bias,
+                           svla_bf16* y, void* stream);
+/* nn.AvgPool2d(2) (the stem's pool, Bottleneck.avgpool and downsample."-1" of the strided blocks): [B,H,W,C] -> [B, H/2, W/2, C], floor, fp32 sum; C % 8 == 0. */
+int svla_avgpool2_nhwc_bf16(const svla_bf16* x, int B, int H, int W, int C, svla_bf16* y, void* stream);
+
 /* In-place dropout of a [rows, N] bf16 activation, element index row*N + col: the two stand-alone sites of the frozen T5 encoder
  * (after the token embedding, after the final layer norm) that stays in train() mode with the rest of the policy
  * (allenact_dino_transformer.py:193,599-603). */

@@ -9,8 +9,8 @@ encoder (text_cond_visual_encoder.py:56-268) -> + last-action / in-hand / time e
 the batch-first IL batch format, the fused cross-entropy kernel and decoupled weight decay in the Adam kernel.
 
 The frozen image encoder stays outside, as on the RL path: visual sensors are either pre-encoded features ``[B,T,C,7,12]`` (C = 384 DINOv2-S,
-768 DINOv2-B / SigLIP-B, 1024 SigLIP-L, 2048 CLIP RN50) or uint8 frames ``[B,T,H,W,3]`` (then the frozen ViT of ``preproc`` runs first: DINOv2 on
-224 x 384, SigLIP on 256 x 256 frames).  The frozen text encoder is t5-small or, for the ``siglip_*`` presets, the SigLIP text tower
+768 DINOv2-B / SigLIP-B, 1024 SigLIP-L, 2048 CLIP RN50) or uint8 frames ``[B,T,H,W,3]`` (then the frozen trunk of ``preproc`` runs first: DINOv2 and
+CLIP RN50 on 224 x 384, SigLIP on 256 x 256 frames).  The frozen text encoder is t5-small or, for the ``siglip_*`` presets, the SigLIP text tower
 (``siglip_text.SigLIPTextFrozen``: ``goals`` is then the tokenizer's id tensor [B, 64], preprocessors.py:334-343).  ``state_dict`` uses the reference's names
 (``actor.weight``, no critic head), so Lightning checkpoints (``model.`` prefix) interchange.
 """
@@ -48,7 +48,7 @@ class _CEFn(torch.autograd.Function):
 class EarlyFusionCnnTransformer(Tower):
     # model_version -> (fusion layers, decoder layers, image-feature width, text encoder); early_fusion_tsfm_models.py:221-312.  Every preset whose
     # fusion transformer and decoder are TransformerConfig(n, 512, 8), with the llama decoder (``use_llama_decoder`` defaults to True, :46):
-    # DINOv2-S / -B, SigLIP-B / -L (image trunk + text tower) and CLIP RN50 (pre-encoded features only: its conv trunk is not built).
+    # DINOv2-S / -B, SigLIP-B / -L (image trunk + text tower) and CLIP RN50 (conv trunk: preproc.ClipResNet on csrc/conv.hip).
     # and the 768-wide presets whose heads are 64 wide (12 heads: siglip_base_6_3 / _6_6 / _12_12; same kernels at D = 768, llama hidden 2048).
     # TransformerConfig(n, 768, 8) = heads of 96 (base_6, and the fusion transformer of siglip_base_3_6) builds too, with its attention on the 96-wide MFMA kernels (csrc/attn_hd96.hip).
     # Four more names cannot be constructed in the reference as shipped: small_3_nonTxEnc / siglip_base_3_nonTxEnc (``globals()["NonTxMultiCameraVisualEncoder"]``, :64, is a KeyError: the class is not
@@ -158,12 +158,13 @@ class EarlyFusionCnnTransformer(Tower):
         return p
 
     def _frozen_image_encoder(self, key, dev):
-        """IMAGE_ENCODERS of image_encoders.py:103-112 for raw uint8 frames, by preset: DINOv2 (224 x 384) or the SigLIP trunk (256 x 256)."""
-        from .preproc import DinoViTPreprocessor, SigLIPPreprocessor
+        """IMAGE_ENCODERS of image_encoders.py:103-112 for raw uint8 frames, by preset: DINOv2 (224 x 384), the SigLIP trunk (256 x 256) or,
+        for clip_resnet_50_3 (2048-wide features), the CLIP RN50 conv trunk (224 x 384)."""
+        from .preproc import ClipResNetPreprocessor, DinoViTPreprocessor, SigLIPPreprocessor
         if self.text_encoder_name.startswith("SigLIP"):
             return SigLIPPreprocessor(key, key, siglip_model_type={768: "ViT-B-16-SigLIP-256", 1024: "ViT-L-16-SigLIP-256"}[self.dino_dim], device=dev)
         if self.dino_dim == 2048:
-            raise NotImplementedError("clip_resnet_50_3: the CLIP RN50 conv trunk is not built; pass its pre-encoded (2048, 7, 12) features")
+            return ClipResNetPreprocessor(key, key, device=dev)
         return DinoViTPreprocessor(key, key, dino_model_type={384: "dinov2_vits14", 768: "dinov2_vitb14", 1024: "dinov2_vitl14"}[self.dino_dim], device=dev)
 
     # ---- reference forward API --------------------------------------------------------------------------------------------------

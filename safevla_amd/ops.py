@@ -770,3 +770,47 @@ def vit_tokens(patch, cls, pos, B, NP, C, out):
 
 def adaptive_pool_tokens(x, B, skip, gh, gw, C, oh, ow, cam=0, ncam=1, tok_out=None, chw_out=None):
     lib().call("svla_adaptive_pool_tokens", _p(x), B, skip, gh, gw, C, oh, ow, cam, ncam, _p(tok_out), _p(chw_out), _stream())
+
+
+# ------------------------------------------------------------------------------------------------ frozen CLIP RN50 trunk (csrc/conv.hip)
+EPI_BIAS, EPI_RELU, EPI_RES_RELU = 0, 1, 2
+
+
+def conv_nhwc(x, w, bias, B, H, W, taps, epi=EPI_BIAS, residual=None, out=None, ldy=None, y_group=0, y_group_stride=0):
+    """out = epi(conv(x, w) + bias): x bf16 [B,H,W,Cin] (rows [B*H*W, Cin]), w bf16 [Cout, taps, Cin] with taps = 9 (3x3, stride 1, pad 1) or 1, bias fp32 [Cout].
+    ``epi``: EPI_BIAS, EPI_RELU, or EPI_RES_RELU = ReLU(conv + bias + residual) with ``residual`` bf16 rows [B*H*W, Cout].  Output pixel m goes to row
+    (m // y_group) * y_group_stride + m % y_group of ``out`` (row stride ``ldy``) when y_group > 0, else to row m."""
+    for n, t_ in (("x", x), ("w", w)) + ((("residual", residual),) if residual is not None else ()):
+        _chk(t_, BF16, n)
+    _chk(bias, F32, "bias")
+    Cout, Cin = w.shape[0], w.shape[-1]
+    assert x.is_contiguous() and w.is_contiguous() and x.numel() == B * H * W * Cin and w.numel() == Cout * taps * Cin and bias.numel() == Cout
+    if out is None:
+        out = torch.empty(B * H * W, Cout, device=x.device, dtype=BF16)
+    _chk(out, BF16, "out")
+    lib().call("svla_conv_nhwc_bf16", _p(x), _p(w), _p(bias), _p(residual), Cout if residual is not None else 0, _p(out), Cout if ldy is None else ldy,
+               int(y_group), int(y_group_stride), B, H, W, Cin, Cout, int(taps), int(epi), _stream())
+    return out
+
+
+def conv_stem_u8(frames_u8, mean3, std3, w, bias, out=None):
+    """u8 [B,H,W,3] -> normalise -> 3x3 stride-2 conv (w fp32 [27, 32], k = (ky*3 + kx)*3 + c) + bias -> ReLU -> bf16 [B, ceil(H/2), ceil(W/2), 32]"""
+    B, H, W = _aug_frames(frames_u8)
+    _chk(w, F32, "w")
+    _chk(bias, F32, "bias")
+    assert w.is_contiguous() and w.numel() == 27 * 32 and bias.numel() == 32
+    if out is None:
+        out = torch.empty(B, (H + 1) // 2, (W + 1) // 2, 32, device=frames_u8.device, dtype=BF16)
+    lib().call("svla_conv_stem_u8_bf16", _p(frames_u8), B, H, W, (ctypes.c_float * 3)(*[float(v) for v in mean3]), (ctypes.c_float * 3)(*[float(v) for v in std3]),
+               _p(w), _p(bias), _p(out), _stream())
+    return out
+
+
+def avgpool2_nhwc(x, B, H, W, C, out=None):
+    """nn.AvgPool2d(2) on bf16 [B,H,W,C] -> [B, H//2, W//2, C]"""
+    _chk(x, BF16, "x")
+    assert x.is_contiguous() and x.numel() == B * H * W * C
+    if out is None:
+        out = torch.empty(B, H // 2, W // 2, C, device=x.device, dtype=BF16)
+    lib().call("svla_avgpool2_nhwc_bf16", _p(x), B, H, W, C, _p(out), _stream())
+    return out

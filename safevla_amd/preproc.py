@@ -14,6 +14,9 @@ against DINOv2 proper; pinned against the fp32 oracle restatement (oracle/ref_vi
 Geometry-generic: DINOv2 ViT-S/B/L-14 (widths 384 / 768 / 1024, 433 tokens) and the SigLIP ViT-B/L-16 trunk
 (256 tokens, no class token) run on the same kernels -- ``SigLIPPreprocessor`` mirrors siglip_preprocessors.py:18-104.
 
+The CLIP RN50 conv trunk of ``clip_resnet_50_3`` (``ClipResNet`` / ``ClipResNetPreprocessor`` below; image_encoders.py:11-48) is the one convolutional encoder:
+stem + 16 bottlenecks on the implicit-GEMM convolution of csrc/conv.hip, eval-mode BatchNorm folded into the weights at sync time.
+
 MI355X path: normalise + crop + im2col fused in one kernel, patch embedding and all block linears on the bf16 MFMA GEMM
 (LayerScale folded into the frozen weights at sync time), fused attention at S = 433, output written directly in the rollout
 storage's bf16 token layout [B, ncam, 84, 384] (and/or the reference's fp32 (B,384,7,12)).
@@ -430,3 +433,204 @@ class SigLIPPreprocessor(_ViTPreprocessorBase):
     def __init__(self, rgb_input_uuid: str, output_uuid: str, siglip_model_type: str = "ViT-B-16-SigLIP-256", device="cuda", flatten: bool = True, augmenter=None, **kw):
         assert siglip_model_type in ("ViT-B-16-SigLIP-256", "ViT-L-16-SigLIP-256"), siglip_model_type
         self._setup(rgb_input_uuid, output_uuid, siglip_model_type, device, flatten, augmenter)
+
+
+# ---- CLIP RN50 conv trunk (clip_resnet_50_3) ----------------------------------------------------------------------------------------------
+CLIP_RGB_MEANS, CLIP_RGB_STDS = DINO_RGB_MEANS, DINO_RGB_STDS      # preprocessors.py:27 -- the DINO constants above ARE the CLIP mean / std
+BN_EPS = 1e-5
+
+
+class _FoldedConv(NamedTuple):
+    """one folded convolution as the kernels take it: w bf16 [Cout, taps, Cin], b fp32 [Cout]"""
+    w: torch.Tensor
+    b: torch.Tensor
+    cin: int
+    cout: int
+    taps: int
+
+
+class ClipResNet(nn.Module):
+    """Frozen CLIP ``ModifiedResNet`` trunk without its attention pool (image_encoders.py:11-48: ``ClipResNet``, ``pool=False``), under the parameter names of CLIP's
+    ``visual`` module: ``conv1.weight``, ``bn1.{weight,bias,running_mean,running_var}``, ..., ``layer2.0.downsample.0.weight``, ``layer2.0.downsample.1.running_var``.
+    The ``clip`` package is third-party and not in the reference tree; its published forward is restated:
+
+      stem   conv1 3->w/2 3x3 stride 2, conv2 w/2->w/2 3x3, conv3 w/2->w 3x3 (each: no bias, BatchNorm, ReLU), AvgPool2d(2)
+      block  conv1 1x1 -> planes, conv2 3x3 (stride 1) -> planes (each BN + ReLU), AvgPool2d(stride) if stride > 1, conv3 1x1 -> 4 planes + BN;
+             identity = downsample (AvgPool2d(stride), 1x1 conv, BN) in the first block of every stage; out = ReLU(conv3 path + identity)
+      stages planes w, 2w, 4w, 8w with strides 1, 2, 2, 2 and ``layers`` blocks; output 32 w channels at 1/32 of the frame: (2048, 7, 12) at 224 x 384.
+
+    Random-init geometry (CLIP's weights are a download); ``load_state_dict`` takes a CLIP ``visual.*`` state dict with the prefix stripped (``attnpool.*`` and
+    ``num_batches_tracked`` entries are ignored).  ``sync()`` folds every eval-mode BatchNorm into its convolution and re-lays the weights for the kernels;
+    ``forward`` is then a chain of launches on NHWC bf16 rows: the fused u8 stem, the implicit-GEMM convolution (csrc/conv.hip) for every 3x3, the narrow 1x1 and the
+    residual + ReLU 1x1, the bf16 NT GEMM for the other 1x1 convolutions."""
+    CHUNK = 16      # frames per pass: the largest activation (layer1's output, H/4 x W/4 x 256 bf16) is 2.75 MB per 224 x 384 frame
+
+    def __init__(self, device, width: int = 64, layers=(3, 4, 6, 3)):
+        super().__init__()
+        assert width % 64 == 0, "channel counts must be multiples of 32"
+        d = torch.device(device)
+        self.width, self.layers = width, tuple(layers)
+
+        def conv(cout, cin, k, gain=1.0):      # He initialisation; the residual branches end small (gain 0.25) so that 16 blocks do not blow the scale up
+            m = _NS()
+            m.weight = nn.Parameter((torch.randn(cout, cin, k, k) * (gain * math.sqrt(2.0 / (cin * k * k)))).to(d), requires_grad=False)
+            return m
+
+        def bn(c):
+            m = _NS()
+            m.weight = nn.Parameter(torch.ones(c, device=d), requires_grad=False)
+            m.bias = nn.Parameter(torch.zeros(c, device=d), requires_grad=False)
+            m.register_buffer("running_mean", torch.zeros(c, device=d))
+            m.register_buffer("running_var", torch.ones(c, device=d))
+            return m
+
+        self.conv1, self.bn1 = conv(width // 2, 3, 3), bn(width // 2)
+        self.conv2, self.bn2 = conv(width // 2, width // 2, 3), bn(width // 2)
+        self.conv3, self.bn3 = conv(width, width // 2, 3), bn(width)
+        inplanes = width
+        for i, n in enumerate(self.layers):
+            planes, stride = width << i, (1 if i == 0 else 2)
+            blocks = []
+            for j in range(n):
+                b = _NS()
+                b.stride = stride if j == 0 else 1
+                b.conv1, b.bn1 = conv(planes, inplanes, 1), bn(planes)
+                b.conv2, b.bn2 = conv(planes, planes, 3), bn(planes)
+                b.conv3, b.bn3 = conv(4 * planes, planes, 1, gain=0.25), bn(4 * planes)
+                if b.stride > 1 or inplanes != 4 * planes:
+                    b.downsample = _NS()          # keys "-1" (the pool: no parameters), "0", "1" of CLIP's Sequential
+                    b.downsample.add_module("0", conv(4 * planes, inplanes, 1))
+                    b.downsample.add_module("1", bn(4 * planes))
+                inplanes = 4 * planes
+                blocks.append(b)
+            setattr(self, f"layer{i + 1}", nn.Sequential(*blocks))
+        self.out_channels = inplanes
+        self._rt = None
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        sd = {k: v for k, v in state_dict.items() if not k.startswith("attnpool.") and not k.endswith("num_batches_tracked")}
+        self._rt = None
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    @staticmethod
+    def fold(conv, bn):
+        """(w * gamma / sqrt(var + eps), beta - mean * gamma / sqrt(var + eps)) in fp32"""
+        s = bn.weight.float() / torch.sqrt(bn.running_var.float() + BN_EPS)
+        return conv.weight.float() * s[:, None, None, None], bn.bias.float() - bn.running_mean.float() * s
+
+    def sync(self):
+        def lay(conv, bn):      # [Cout, Cin, kh, kw] -> K-major [Cout, taps, Cin] bf16 + fp32 bias
+            w, b = self.fold(conv, bn)
+            co, ci, kh, kw = w.shape
+            return _FoldedConv(w.permute(0, 2, 3, 1).reshape(co, kh * kw, ci).to(BF16).contiguous(), b.contiguous(), ci, co, kh * kw)
+
+        rt = {}
+        w, b = self.fold(self.conv1, self.bn1)      # stem: fp32 [27, Cout] holding the bf16-rounded folded weights (every folded weight of the trunk is a bf16 value)
+        rt["stem"] = (w.to(BF16).float().permute(2, 3, 1, 0).reshape(27, -1).contiguous(), b.contiguous())
+        rt["conv2"], rt["conv3"] = lay(self.conv2, self.bn2), lay(self.conv3, self.bn3)
+        rt["blocks"] = []
+        for i in range(len(self.layers)):
+            for blk in getattr(self, f"layer{i + 1}"):
+                down = lay(getattr(blk.downsample, "0"), getattr(blk.downsample, "1")) if hasattr(blk, "downsample") else None
+                rt["blocks"].append((blk.stride, lay(blk.conv1, blk.bn1), lay(blk.conv2, blk.bn2), lay(blk.conv3, blk.bn3), down))
+        self._rt = rt
+
+    @staticmethod
+    def _conv1x1(x, L, B, H, W, relu: bool):
+        M = B * H * W
+        if L.cout % 128 == 0 and L.cin % 64 == 0:      # the bf16 NT GEMM's shapes; the two 64-wide 1x1 of layer1 stay on the convolution kernel
+            return ops.gemm_nt(x.view(M, L.cin), L.w.view(L.cout, L.cin), M, L.cout, L.cin, bias=L.b, act=ops.ACT_RELU if relu else ops.ACT_NONE)
+        return ops.conv_nhwc(x, L.w, L.b, B, H, W, 1, ops.EPI_RELU if relu else ops.EPI_BIAS)
+
+    def _chunk(self, fr, mean, std, out, y_group, y_group_stride):
+        rt = self._rt
+        B, H, W, _ = fr.shape
+        assert rt["stem"][0].shape[1] == 32, "the fused stem kernel is built for CLIP RN50's 32 stem channels (width 64)"
+        h = ops.conv_stem_u8(fr, mean, std, *rt["stem"])
+        H, W = H // 2, W // 2
+        h = ops.conv_nhwc(h, rt["conv2"].w, rt["conv2"].b, B, H, W, 9, ops.EPI_RELU)
+        h = ops.conv_nhwc(h, rt["conv3"].w, rt["conv3"].b, B, H, W, 9, ops.EPI_RELU)
+        h = ops.avgpool2_nhwc(h, B, H, W, rt["conv3"].cout)
+        H, W = H // 2, W // 2
+        last = len(rt["blocks"]) - 1
+        for k, (stride, c1, c2, c3, down) in enumerate(rt["blocks"]):
+            o = self._conv1x1(h, c1, B, H, W, True)
+            o = ops.conv_nhwc(o, c2.w, c2.b, B, H, W, 9, ops.EPI_RELU)
+            idn = h
+            if stride > 1:
+                o = ops.avgpool2_nhwc(o, B, H, W, c2.cout)
+                idn = ops.avgpool2_nhwc(h, B, H, W, c1.cin)
+                H, W = H // 2, W // 2
+            if down is not None:
+                idn = self._conv1x1(idn, down, B, H, W, False)
+            if k == last:      # the trunk's output rows go where the caller wants them (dense rows, or one camera slot of the token tensor)
+                ops.conv_nhwc(o, c3.w, c3.b, B, H, W, 1, ops.EPI_RES_RELU, residual=idn, out=out, ldy=c3.cout, y_group=y_group, y_group_stride=y_group_stride)
+            else:
+                h = ops.conv_nhwc(o, c3.w, c3.b, B, H, W, 1, ops.EPI_RES_RELU, residual=idn)
+
+    @torch.no_grad()
+    def forward(self, frames_u8: torch.Tensor, mean=CLIP_RGB_MEANS, std=CLIP_RGB_STDS, out: Optional[torch.Tensor] = None, cam: Optional[int] = None) -> torch.Tensor:
+        """frames_u8 [B,H,W,3] uint8 (H, W multiples of 32) -> bf16 rows [B, H/32 * W/32, C]: a new tensor, or ``out``; with ``cam`` the rows of frame b are written
+        into ``out[b, cam]`` of a token tensor [B, ncam, H/32 * W/32, C]."""
+        B, H, W, _ = frames_u8.shape
+        assert frames_u8.dtype == torch.uint8 and H % 32 == 0 and W % 32 == 0 and H > 0 and W > 0, f"uint8 frames with H, W multiples of 32; got {tuple(frames_u8.shape)}"
+        if self._rt is None:
+            self.sync()
+        P, C = (H // 32) * (W // 32), self.out_channels
+        if out is None:
+            assert cam is None
+            out = torch.empty(B, P, C, device=frames_u8.device, dtype=BF16)
+        assert out.dtype == BF16 and out.is_contiguous() and out.shape[0] == B and tuple(out.shape[-2:]) == (P, C), tuple(out.shape)
+        ncam = out.shape[1] if cam is not None else 1
+        assert (cam or 0) < ncam
+        fr = frames_u8.contiguous()
+        for b0 in range(0, B, self.CHUNK):
+            b1 = min(B, b0 + self.CHUNK)
+            dst = out[b0:, cam] if cam is not None else out[b0:]
+            self._chunk(fr[b0:b1], mean, std, dst, P if cam is not None else 0, ncam * P if cam is not None else 0)
+        return out
+
+
+class ClipResNetPreprocessor(_ViTPreprocessorBase):
+    """image_encoders.py:11-48 + preprocessors.py:27: 224 x 384 uint8 frames -> CLIP normalisation -> frozen CLIP RN50 trunk -> (B, 2048, 7, 12).  Same surface as the
+    ViT preprocessors: ``process`` returns the reference's fp32 (B, 2048, 7, 12), ``process_tokens`` / ``process_tokens_all_cameras`` write the storage-native bf16
+    tokens [B, ncam, 84, 2048] -- the trunk's last block writes its rows straight into the camera slot."""
+    MEAN, STD, HW = CLIP_RGB_MEANS, CLIP_RGB_STDS, (224, 384)
+
+    def __init__(self, rgb_input_uuid: str, output_uuid: str, device="cuda", flatten: bool = True, augmenter=None, **kw):
+        self.input_uuids, self.uuid, self.device = [rgb_input_uuid], output_uuid, torch.device(device)
+        self.augmenters = [] if augmenter is None else (list(augmenter) if isinstance(augmenter, (list, tuple)) else [augmenter])
+        self.resnet = ClipResNet(self.device)
+        C = self.resnet.out_channels
+        self.observation_space = Box(-float("inf"), float("inf"), (7 * 12, C) if flatten else (7, 12, C))
+
+    def _check(self, fr):
+        assert tuple(fr.shape[1:3]) == self.HW, f"Expected shape is {self.HW[0]}x{self.HW[1]}; got {tuple(fr.shape[1:3])}"
+        return fr
+
+    @torch.no_grad()
+    def process(self, obs: Dict[str, torch.Tensor], *a, **k) -> torch.Tensor:
+        assert len(self.augmenters) <= 1, "process serves one camera: pass one augmenter"
+        fr = self._check(self._augment(obs[self.input_uuids[0]].to(self.device)))
+        B, C = fr.shape[0], self.resnet.out_channels
+        x = self.resnet(fr, self.MEAN, self.STD)
+        out = torch.empty(B, C, 7, 12, device=self.device, dtype=torch.float32)
+        ops.adaptive_pool_tokens(x, B, 0, 7, 12, C, 7, 12, chw_out=out)      # 7 x 12 -> 7 x 12: the token rows transposed to fp32 channels-first
+        return out
+
+    @torch.no_grad()
+    def process_tokens(self, frames_u8: torch.Tensor, out_tokens: torch.Tensor, cam: int, ncam: int = 2):
+        assert out_tokens.shape[1] == ncam
+        self.resnet(self._check(self._augment(frames_u8.to(self.device), cam)), self.MEAN, self.STD, out=out_tokens, cam=cam)
+
+    @torch.no_grad()
+    def process_tokens_all_cameras(self, frames_u8: torch.Tensor, out_tokens: torch.Tensor):
+        """frames_u8 [ncam * B, H, W, 3], camera-major -> out_tokens [B, ncam, 84, 2048]; with augmenters (one per camera) each camera's slice is augmented first"""
+        B, ncam = out_tokens.shape[0], out_tokens.shape[1]
+        assert frames_u8.shape[0] == ncam * B
+        fr = self._check(frames_u8.to(self.device))
+        if self.augmenters:
+            assert len(self.augmenters) == ncam, f"{ncam} cameras need {ncam} augmenters, got {len(self.augmenters)}"
+        for cam in range(ncam):
+            x = fr[cam * B:(cam + 1) * B]
+            self.resnet(self.augmenters[cam].augment_u8(x) if self.augmenters else x, self.MEAN, self.STD, out=out_tokens, cam=cam)
