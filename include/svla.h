@@ -341,6 +341,15 @@ int svla_aug_jitter_blur_u8(const unsigned char* x, unsigned char* y, int B, int
 int svla_aug_resize_post_sharp_u8(const unsigned char* x, unsigned char* y, int B, int H, int W, int top, int left, int bh, int bw, int posterize,
                                   int sharpen, void* stream);
 
+/* ---- camera frames -> the model's input size (SigLIP presets: 224 x 384 -> 256 x 256) ---------------------------------------------- */
+/* tensor_image_preprocessor prepends torchvision Resize(size, bicubic, antialias=True) when the size is not the camera's
+ * (architecture/models/transformer_models/preprocessors.py:35-43); on the reference's device-resident uint8 frames that is
+ * interpolate(x.float(), mode="bicubic", antialias=True, align_corners=False) -> clamp(0, 255) -> round half to even -> u8.  u8 [B,H,W,3] -> u8 [B,OH,OW,3] in one
+ * launch (x != y): per axis scale = in / out, support = 2 max(scale, 1), taps [max(0, int(c - support + 0.5)), min(in, int(c + support + 0.5))) around
+ * c = scale (i + 0.5), Keys cubic (a = -0.5) of (j - c + 0.5) / max(scale, 1), normalised; horizontal pass, then vertical, fp32 between them (not rounded).
+ * (OH, OW) == (H, W) is an exact copy.  H, W, OH, OW >= 4 and per-axis scales in [1/4, 4]; anything else is SVLA_EINVAL, nothing launched. */
+int svla_resize_bicubic_aa_u8(const unsigned char* x, unsigned char* y, int B, int H, int W, int OH, int OW, void* stream);
+
 /* ---- frozen CLIP RN50 image trunk (clip_resnet_50_3; rollout / data-loading time) ------------------------------------------------
  * ClipResNet (architecture/models/transformer_models/image_encoders.py:11-48, pool=False -> (2048, 7, 12)) runs CLIP's ModifiedResNet [3P openai/CLIP], layers
  * (3, 4, 6, 3), width 64, on 224 x 384 frames normalised with the CLIP mean / std (architecture/models/transformer_models/preprocessors.py:27).  Activations are

@@ -10,7 +10,7 @@ the batch-first IL batch format, the fused cross-entropy kernel and decoupled we
 
 The frozen image encoder stays outside, as on the RL path: visual sensors are either pre-encoded features ``[B,T,C,7,12]`` (C = 384 DINOv2-S,
 768 DINOv2-B / SigLIP-B, 1024 SigLIP-L, 2048 CLIP RN50) or uint8 frames ``[B,T,H,W,3]`` (then the frozen trunk of ``preproc`` runs first: DINOv2 and
-CLIP RN50 on 224 x 384, SigLIP on 256 x 256 frames).  The frozen text encoder is t5-small or, for the ``siglip_*`` presets, the SigLIP text tower
+CLIP RN50 on 224 x 384, SigLIP on 256 x 256 frames or on camera frames resized to that, preprocessors.py:35-43).  The frozen text encoder is t5-small or, for the ``siglip_*`` presets, the SigLIP text tower
 (``siglip_text.SigLIPTextFrozen``: ``goals`` is then the tokenizer's id tensor [B, 64], preprocessors.py:334-343).  ``state_dict`` uses the reference's names
 (``actor.weight``, no critic head), so Lightning checkpoints (``model.`` prefix) interchange.
 """
@@ -158,11 +158,14 @@ class EarlyFusionCnnTransformer(Tower):
         return p
 
     def _frozen_image_encoder(self, key, dev):
-        """IMAGE_ENCODERS of image_encoders.py:103-112 for raw uint8 frames, by preset: DINOv2 (224 x 384), the SigLIP trunk (256 x 256) or,
+        """IMAGE_ENCODERS of image_encoders.py:103-112 for raw uint8 frames, by preset: DINOv2 (224 x 384), the SigLIP trunk (256 x 256; other sizes are resized) or,
         for clip_resnet_50_3 (2048-wide features), the CLIP RN50 conv trunk (224 x 384)."""
-        from .preproc import ClipResNetPreprocessor, DinoViTPreprocessor, SigLIPPreprocessor
+        from .preproc import ClipResNetPreprocessor, DinoViTPreprocessor, SigLIPDataAugmentationPreprocessor, SigLIPPreprocessor
         if self.text_encoder_name.startswith("SigLIP"):
-            return SigLIPPreprocessor(key, key, siglip_model_type={768: "ViT-B-16-SigLIP-256", 1024: "ViT-L-16-SigLIP-256"}[self.dino_dim], device=dev)
+            # SigLipPreprocessor of preprocessors.py:319-328: tensor_image_preprocessor(size=(256, 256)) resizes camera-sized frames in front of the trunk (one
+            # resizing front per camera; 256 x 256 frames pass through it untouched)
+            resize = [SigLIPDataAugmentationPreprocessor(k, k, device=dev) for k in (NAV, MANIP)]
+            return SigLIPPreprocessor(key, key, siglip_model_type={768: "ViT-B-16-SigLIP-256", 1024: "ViT-L-16-SigLIP-256"}[self.dino_dim], device=dev, augmenter=resize)
         if self.dino_dim == 2048:
             return ClipResNetPreprocessor(key, key, device=dev)
         return DinoViTPreprocessor(key, key, dino_model_type={384: "dinov2_vits14", 768: "dinov2_vitb14", 1024: "dinov2_vitl14"}[self.dino_dim], device=dev)

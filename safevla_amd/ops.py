@@ -764,6 +764,20 @@ def aug_resize_post_sharp(x_u8, box=None, posterize=False, sharpen=False, out=No
     return y
 
 
+def resize_bicubic_aa_u8(x_u8, out_hw, out=None):
+    """u8 [B,H,W,3] -> u8 [B,OH,OW,3]: torchvision's Resize(out_hw, bicubic, antialias=True) as it acts on device-resident uint8 frames (fp32 interpolation, clamp,
+    round half to even; csrc/resize.hip) -- one launch.  Equal sizes: an exact copy.  The kernel's limits (sizes >= 4, per-axis scale in [1/4, 4]) are the C entry's:
+    outside them it raises SvlaError and nothing is launched."""
+    B, H, W = _aug_frames(x_u8)
+    OH, OW = (int(v) for v in out_hw)
+    y = torch.empty(B, max(OH, 0), max(OW, 0), 3, device=x_u8.device, dtype=torch.uint8) if out is None else out
+    _aug_frames(y, "out")
+    if tuple(y.shape) != (B, OH, OW, 3):
+        raise ValueError(f"out: expected {(B, OH, OW, 3)}, got {tuple(y.shape)}")
+    lib().call("svla_resize_bicubic_aa_u8", _p(x_u8), _p(y), B, H, W, OH, OW, _stream())
+    return y
+
+
 def vit_tokens(patch, cls, pos, B, NP, C, out):
     lib().call("svla_vit_tokens", _p(patch), _p(cls), _p(pos), B, NP, C, _p(out), _stream())
 

@@ -223,6 +223,56 @@ class DataAugmentationPreprocessor:
         return ops.normalize_u8(x, self.mean if self.normalize else (0, 0, 0), self.stdev if self.normalize else (1, 1, 1))
 
 
+SIGLIP_RGB_MEANS, SIGLIP_RGB_STDS = (0.5, 0.5, 0.5), (0.5, 0.5, 0.5)
+
+
+class SigLIPDataAugmentationPreprocessor(DataAugmentationPreprocessor):
+    """The camera-frame front of the SigLIP presets: ``tensor_image_preprocessor(size=(256, 256))`` of preprocessors.py:22-60 as the IL ``SigLipPreprocessor``
+    (:319-328) and the online ``DataAugmentationPreprocessor`` of siglip_preprocessors.py:144-210 use it.  Frames whose size is not ``size`` go through
+    torchvision's ``Resize(size, bicubic, antialias=True)`` first (one launch, ``ops.resize_bicubic_aa_u8``: fp32 interpolation of the uint8 frames, clamp, round,
+    uint8); frames that already have it pass through untouched.  With ``use_augmentation`` the sampled v2 transform then runs at the resized geometry -- the
+    reference builds the list with ``size=(256, 256)``, so its crop box and blur act on the 256 x 256 image -- and ``/255`` with ``Normalize(mean, stdev)`` follow.
+
+    ``augment_u8`` makes this class an ``augmenter=`` of ``SigLIPPreprocessor``, whose own input stays 256 x 256.
+
+    Not reproduced: the reference's online SigLIP class draws the FULL random v2 list afresh on every call, including its four-step posterize chain with bits 7 to
+    4.  The kernels here implement the sampled-specific list (one transform kept for ``num_steps_to_change`` calls, posterize to 7 bits), as the DINOv2
+    preprocessor's augmentation does."""
+
+    def __init__(self, rgb_input_uuid: str, output_uuid: str, device="cuda", height=224, width=384, size=(256, 256), mean=SIGLIP_RGB_MEANS, stdev=SIGLIP_RGB_STDS,
+                 normalize=True, use_augmentation=False, num_steps_to_change=500, generator: Optional[torch.Generator] = None, **kw):
+        super().__init__(rgb_input_uuid, output_uuid, device=device, normalize=normalize, mean=mean, stdev=stdev, height=height, width=width,
+                         use_augmentation=use_augmentation, num_steps_to_change=num_steps_to_change, generator=generator)
+        self.size = (int(size[0]), int(size[1]))
+        self.observation_space = Box(-float("inf"), float("inf"), (*self.size, 3))
+
+    def augment_u8(self, frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """u8 [B,H,W,3] -> u8 [B,*size,3]: resize when the size differs, then (use_augmentation) the sampled transform, which counts as one call of the schedule"""
+        x = self._frames(frames_u8)
+        resize = tuple(x.shape[1:3]) != self.size
+        if not self.use_augmentation:
+            if resize:
+                return ops.resize_bicubic_aa_u8(x, self.size, out=out)
+            if out is None:
+                return x
+            out.copy_(x)
+            return out
+        if resize:
+            x = ops.resize_bicubic_aa_u8(x, self.size)
+        return apply_augment_u8(x, self.next_call(*self.size), out=out)
+
+    def augment_u8_stages(self, frames_u8: torch.Tensor):
+        x = self._frames(frames_u8)
+        if tuple(x.shape[1:3]) != self.size:
+            x = ops.resize_bicubic_aa_u8(x, self.size)
+        call = self.next_call(*self.size)
+        return call, apply_augment_u8(x, call, debug=True)
+
+    def process(self, obs: Dict[str, torch.Tensor], *a, **k) -> torch.Tensor:
+        x = self.augment_u8(obs[self.input_uuids[0]])
+        return ops.normalize_u8(x, self.mean if self.normalize else (0, 0, 0), self.stdev if self.normalize else (1, 1, 1))
+
+
 # geometry presets: (dim, depth, heads, patch, native_grid, class token, LayerScale)
 VIT_PRESETS = {
     # DINOv2 (torch.hub facebookresearch/dinov2; dino_preprocessors.py:14-18,54-76): pos_embed is the 37 x 37 grid of 518 / 14
@@ -403,7 +453,9 @@ class _ViTPreprocessorBase:
         fr = frames_u8.to(self.device)
         if self.augmenters:
             assert len(self.augmenters) == ncam, f"{ncam} cameras need {ncam} augmenters, got {len(self.augmenters)}"
-            aug = torch.empty_like(fr, memory_format=torch.contiguous_format)
+            # an augmenter that resizes (SigLIPDataAugmentationPreprocessor) names its output size in ``size``: both cameras' resized frames share one buffer
+            oh, ow = getattr(self.augmenters[0], "size", None) or fr.shape[1:3]
+            aug = torch.empty(fr.shape[0], oh, ow, 3, device=fr.device, dtype=fr.dtype)
             for cam, a in enumerate(self.augmenters):
                 a.augment_u8(fr[cam * B:(cam + 1) * B], out=aug[cam * B:(cam + 1) * B])
             fr = aug

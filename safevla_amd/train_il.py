@@ -15,12 +15,14 @@ from . import ops, parallel
 from .il import MANIP, NAV, PAD_TOKEN, START_TOKEN, EarlyFusionCnnTransformer, ILTrainer
 
 
-def synthetic_batch(B: int, T: int, L: int, device, generator: torch.Generator, raw_frames: bool = False, feat_dim: int = 384, siglip: bool = False):
-    """``siglip``: 256 x 256 frames and the open_clip tokenizer's goal format (an id tensor [B, 64] padded with 1, preprocessors.py:300-343)."""
+def synthetic_batch(B: int, T: int, L: int, device, generator: torch.Generator, raw_frames: bool = False, feat_dim: int = 384, siglip: bool = False,
+                    frame_hw=None):
+    """``siglip``: 256 x 256 frames and the open_clip tokenizer's goal format (an id tensor [B, 64] padded with 1, preprocessors.py:300-343).
+    ``frame_hw``: another raw-frame size, e.g. the camera's (224, 384), which the SigLIP presets resize in front of their trunk."""
     g = generator
     r = lambda *s, hi: torch.randint(0, hi, s, device=device, generator=g)
     if raw_frames:
-        H, W = (256, 256) if siglip else (224, 384)
+        H, W = frame_hw or ((256, 256) if siglip else (224, 384))
         nav, man = r(B, T, H, W, 3, hi=256).to(torch.uint8), r(B, T, H, W, 3, hi=256).to(torch.uint8)
     else:
         nav, man = (torch.randn(B, T, feat_dim, 7, 12, device=device, generator=g) for _ in range(2))
@@ -58,6 +60,7 @@ def main():
     ap.add_argument("--input_sensors", nargs="+", default=[NAV, MANIP, "last_actions", "an_object_is_in_hand"])
     ap.add_argument("--goal_tokens", type=int, default=12)
     ap.add_argument("--raw_frames", action="store_true")
+    ap.add_argument("--frame_hw", type=int, nargs=2, default=None, metavar=("H", "W"), help="size of the synthetic --raw_frames (default: the preset's own input size)")
     ap.add_argument("--init_ckpt", default=None)
     args = ap.parse_args()
     rank, local, world = parallel.init_from_env()
@@ -74,7 +77,8 @@ def main():
     steps = max(1, args.max_samples // (B * world))
     t0 = time.perf_counter()
     for it in range(steps):
-        batch = synthetic_batch(B, T, args.goal_tokens, dev, gen, args.raw_frames, feat_dim=model.dino_dim, siglip=model.text_encoder_name.startswith("SigLIP"))
+        batch = synthetic_batch(B, T, args.goal_tokens, dev, gen, args.raw_frames, feat_dim=model.dino_dim, siglip=model.text_encoder_name.startswith("SigLIP"),
+                                frame_hw=args.frame_hw)
         model.zero_grad()
         out = model(batch)
         (out["loss"] / world).backward()
