@@ -10,23 +10,15 @@
 // Layout trick ("swapped QK^T"): S^T = K.Q^T puts the query index on lane&15, so a query's whole score row is
 // lane-local (+2 cross-lane steps), and the probabilities already sit in the MFMA A-operand layout of P.V;
 // V (and K/Q/dO in the backward) are read as B operands straight from row-major LDS with ds_read_b64_tr_b16.
-#include "common.h"
+#include "attn_common.h"      // dropout index, LDS swizzle and lane bases, fragment helpers: shared with the files below
 #include "attn_hd96.h"      // head_dim 96: its own kernels and LDS layout (attn_hd96.hip)
 #include "attn_long.h"      // backward for 256 < S <= 512: eight-wave kernels with runtime tile loops (attn_long.hip)
 #include "attn_decode_long.h"      // single-query forward for 512 < S <= 1024 (attn_decode_long.hip)
 
-#ifndef ATT_SWZ_OLD
-#define ATT_SWZ_OLD 0
-#endif
-#ifndef ATT_EARLY_TR
-#define ATT_EARLY_TR 0      // measured: no gain at 3 workgroups per CU (other waves hide the LDS latency), spills with dropout
-#endif
 #define HD 64
-#define LDSROW 64   // LDS row = 128 B (one head slice row), 16-byte chunks XOR-swizzled: 48 KiB for two [192, 64] operands,
-                    // so THREE workgroups fit a CU's 160 KiB (the kernels are latency-bound: 1 -> 2 workgroups/CU = 1.74x)
+// LDS row (LDSROW, attn_common.h) = 128 B (one head slice row), 16-byte chunks XOR-swizzled: 48 KiB for two [192, 64] operands,
+// so THREE workgroups fit a CU's 160 KiB (the kernels are latency-bound: 1 -> 2 workgroups/CU = 1.74x)
 #define ATT_THREADS 256
-
-enum { MASK_NONE = 0, MASK_BLOCK_CAUSAL = 1 };
 
 struct AttnArgs {
     const bf16_t *Q, *K, *V; long ld;     // token row stride (elements) of the q/k/v tensors
@@ -47,68 +39,6 @@ struct AttnArgs {
     int xcd_rows;                         // single-pass backward: workgroup -> (row, head) so that every XCD walks whole rows (0: row-major items)
 };
 
-// element index of probability (row r, head h, query q, key k): ((r*H + h)*S + q) * SP4 + k with the key stride SP4 = S rounded
-// up to a multiple of 4, so that the 4 consecutive keys a lane holds share two RNG words (include/svla.h: svla_dropout)
-__device__ __forceinline__ unsigned long long att_drop_row(const AttnArgs& p, int r, int h, int q) {
-    return ((unsigned long long)((size_t)r * p.H + h) * p.S + q) * (unsigned long long)((p.S + 3) & ~3);
-}
-__device__ __forceinline__ bool att_keep1(const DropCfg& c, unsigned long long e) {
-    const unsigned x = drop_bits(c.key, e >> 1);
-    return ((e & 1) ? (x >> 16) : (x & 0xffffu)) >= c.thr;
-}
-
-// physical 16-byte chunk of logical chunk c in row r: c ^ f(x), x = (r >> 1) & 7 (64 banks x 4 B; a row is 32 banks, so the row
-// parity picks the bank half and f only has to spread the eight values of x over the eight 16-byte slots of a half).  Three
-// access patterns constrain f:
-//  * ds_read_b128 row fragments (row = lane & 15, logical chunk = lane >> 4): the hardware serves lanes {0-3,12-15,20-27},
-//    {4-11,16-19,28-31}, ... as groups, i.e. rows with x in {0,1,6,7} on chunk c together with rows with x in {2,3,4,5} on
-//    chunk c ^ 1: conflict-free iff f is a permutation and f({2,3,4,5}) is a union of two chunk pairs {2k, 2k+1};
-//  * ds_read_b64_tr_b16 (32 lanes per pass = 8 rows x 32 B = one chunk PAIR per row): f >> 1 must be distinct over
-//    x = 0..3 and over x = 4..7.  (f = x, the first layout, put rows 2,3 on the chunk pair of rows 0,1: every transposed
-//    read was a 2-way conflict.)
-//  * staging stores (8 lanes = one row): any f.
-// f = 0,2,4,6,5,7,1,3 satisfies all three.
-__device__ __forceinline__ int att_swz(int row) {
-    const int x = (row >> 1) & 7;
-    return ATT_SWZ_OLD ? x : ((((x + ((x >> 2) << 1)) & 3) << 1) | (x >> 2));
-}
-
-// Lane bases of the two access patterns (tile rows are multiples of 16, so the swizzle term depends on the lane only and the
-// tile offset stays a compile-time immediate of the ds_read):
-//   row fragment  : row = tile + (lane & 15), logical chunk (lane >> 4) [+4 for columns 32..63]
-//   transposed    : row = tile + 4 (lane >> 4) + ((lane & 15) >> 2), columns dt*16 + 4 ((lane & 15) & 3) .. +3
-struct RowBase { const bf16_t* lo; const bf16_t* hi; };
-__device__ __forceinline__ RowBase att_row_base(const bf16_t* tile, int lane) {
-    const int ql = lane & 15, g = lane >> 4, f = att_swz(ql);
-    return RowBase{tile + ql * LDSROW + ((g ^ f) << 3), tile + ql * LDSROW + (((g + 4) ^ f) << 3)};
-}
-struct TrBase { const bf16_t* d[4]; };
-__device__ __forceinline__ TrBase att_tr_base(const bf16_t* tile, int lane) {
-    const int ql = lane & 15, g = lane >> 4;
-    const int row = 4 * g + (ql >> 2), f = att_swz(row);
-    TrBase t;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) t.d[dt] = tile + row * LDSROW + (((2 * dt + ((ql & 3) >> 1)) ^ f) << 3) + 4 * (ql & 1);
-    return t;
-}
-__device__ __forceinline__ bf16x8 lds_row8i(const bf16_t* lane_base, int tile_row0) {
-    return *(const bf16x8*)(lane_base + tile_row0 * LDSROW);
-}
-// B/A-operand gather: 8 reduction slots = rows {rA + 4g + 0..3, rB + 4g + 0..3}, column dt*16 + (lane & 15)
-__device__ __forceinline__ bf16x8 lds_tr8i(const bf16_t* lane_base_dt, int rA, int rB) {
-    const bf16x4 lo = lds_tr16_b64(lane_base_dt + rA * LDSROW);
-    const bf16x4 hi = lds_tr16_b64(lane_base_dt + rB * LDSROW);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-__device__ __forceinline__ bf16x8 pack8(const float (&v)[8]) {
-    u32x4 w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = pack_bf2(v[2 * i], v[2 * i + 1]);
-    return __builtin_bit_cast(bf16x8, w);
-}
-#define LOG2E 1.4426950408889634f
-#define LN2 0.6931471805599453f
-
 // stage an [S, 64] head slice into LDS rows (zero-filled up to SP rows): all global loads are issued before the first LDS
 // store so the HBM/L2 latency is paid once, not once per loop trip
 template <int SP, int THREADS = ATT_THREADS>
@@ -127,13 +57,6 @@ __device__ __forceinline__ void stage_head(bf16_t* dst, const bf16_t* src, long 
         const int q = tid + i * THREADS;
         *(u32x4*)(dst + (q >> 3) * LDSROW + (((q & 7) ^ att_swz(q >> 3)) << 3)) = w[i];
     }
-}
-
-__device__ __forceinline__ bool masked(const AttnArgs& p, int q, int key, const int* traj_s, const unsigned char* kv_s) {
-    if (key >= p.S) return true;
-    if (p.mask_mode == MASK_BLOCK_CAUSAL && (key > q || traj_s[key] != traj_s[q])) return true;
-    if (kv_s && !kv_s[key]) return true;
-    return false;
 }
 
 // ================================================================================================ forward
@@ -206,7 +129,7 @@ __device__ __forceinline__ void attn_fwd_kernel_body(AttnArgs p) {
                     float s = a[e] * p.scale;
                     if (p.bias && q < Sq && key < S) s += p.bias[((size_t)h * S + q) * S + key];
                     s *= LOG2E;
-                    if (masked(p, q < Sq ? q : 0, key, traj_s, kvp)) s = -INFINITY;
+                    if (att_masked(p, q < Sq ? q : 0, key, traj_s, kvp)) s = -INFINITY;
                     sc[kt][e] = s;
                     mx = fmaxf(mx, s);
                 }
@@ -232,7 +155,7 @@ __device__ __forceinline__ void attn_fwd_kernel_body(AttnArgs p) {
         lsum += __shfl_xor(lsum, 16, 64);
         lsum += __shfl_xor(lsum, 32, 64);
         if (p.drop.thr) {      // dropout on the normalised probabilities: zero here, 1/(1-p) folded into the final scale
-            const unsigned long long rb = att_drop_row(p, r, h, q < Sq ? q : 0);
+            const unsigned long long rb = att_drop_row(p.S, p.H, r, h, q < Sq ? q : 0);
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) {
                 const unsigned keep = drop_keep4(p.drop, rb + kt * 16 + 4 * g);
@@ -284,7 +207,7 @@ struct AttDrop {               // per (row, head): hash of pair index P0 + delta
 };
 __device__ __forceinline__ AttDrop att_drop_head(const AttnArgs& p, int r, int h) {
     AttDrop d;
-    d.p0 = att_drop_row(p, r, h, 0) >> 1;
+    d.p0 = att_drop_row(p.S, p.H, r, h, 0) >> 1;
     d.a0 = (unsigned)d.p0 * 0x9E3779B1u;
     d.hb = ((unsigned)(d.p0 >> 32) * 0x85EBCA77u) ^ p.drop.key;
     d.wrap = (unsigned)d.p0 > 0xFFFF0000u;
@@ -411,7 +334,7 @@ __device__ __forceinline__ void attn_fwd_persist_kernel_body(AttnArgs p, int nit
                         if ((r1 >> 16) < thr) sc[kt][3] = 0.f;
                     }
                 } else {
-                    const unsigned long long rb = att_drop_row(p, r, h, q < Sq ? q : 0);
+                    const unsigned long long rb = att_drop_row(p.S, p.H, r, h, q < Sq ? q : 0);
 #pragma unroll
                     for (int kt = 0; kt < NKT; ++kt) {
                         const unsigned keep = drop_keep4(p.drop, rb + kt * 16 + 4 * g);
@@ -451,15 +374,6 @@ __device__ __forceinline__ void attn_fwd_persist_kernel_body(AttnArgs p, int nit
 //   dQ  kernel (waves own query tiles, swapped layout, K and V in LDS):   dQ = dS.K
 //   dKV kernel (waves own key tiles, Q and dO in LDS):                    dK = dS^T.Q, dV = P^T.dO
 // P is recomputed from the saved log-sum-exp; D = rowsum(dO * O).
-__device__ __forceinline__ bf16x8 gld8(const bf16_t* p, bool ok) {
-    return ok ? *(const bf16x8*)p : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-}
-__device__ __forceinline__ float dot8(bf16x8 a, bf16x8 b) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += bf2f((bf16_t)a[i]) * bf2f((bf16_t)b[i]);
-    return s;
-}
 
 template <int NKT, bool GENERIC>
 __global__ void __launch_bounds__(ATT_THREADS) attn_bwd_dq_kernel(AttnArgs p) {
@@ -532,14 +446,14 @@ __global__ void __launch_bounds__(ATT_THREADS) attn_bwd_dq_kernel(AttnArgs p) {
                     dp = mfma16(lds_row8i(Vrow.lo, kt * 16), gf0, dp);
                     dp = mfma16(lds_row8i(Vrow.hi, kt * 16), gf1, dp);
                     // dP = keep/(1-p) * (dO V^T): the forward's keep-mask, regenerated
-                    const unsigned dkeep = p.drop.thr ? drop_keep4(p.drop, att_drop_row(p, r, h, qok ? q : 0) + kt * 16 + 4 * g) : 0xfu;
+                    const unsigned dkeep = p.drop.thr ? drop_keep4(p.drop, att_drop_row(p.S, p.H, r, h, qok ? q : 0) + kt * 16 + 4 * g) : 0xfu;
                     if constexpr (GENERIC) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int key = kt * 16 + 4 * g + e;
                             float sv = s[e] * p.scale;
                             if (p.bias && qok && key < S) sv += p.bias[((size_t)h * S + q) * S + key];
-                            const bool mk = !qok || masked(p, qok ? q : 0, key, traj_s, kvp);
+                            const bool mk = !qok || att_masked(p, qok ? q : 0, key, traj_s, kvp);
                             const float pr = mk ? 0.f : __expf(sv - lse_q);
                             dsv[e2 * 4 + e] = pr * (((dkeep >> e) & 1u ? dp[e] * p.drop.scale : 0.f) - D_q) * p.scale;
                         }
@@ -664,9 +578,9 @@ __global__ void __launch_bounds__(ATT_THREADS, NKT <= 12 ? 3 : 1) attn_bwd_dkv_k
                             const int q = qt * 16 + 4 * g + e;
                             float sv = s[e] * p.scale;
                             if (p.bias && q < S && kok) sv += p.bias[((size_t)h * S + q) * S + keyl];
-                            const bool mk = (q >= Sq) || masked(p, q < Sq ? q : 0, keyl, traj_s, kvp);
+                            const bool mk = (q >= Sq) || att_masked(p, q < Sq ? q : 0, keyl, traj_s, kvp);
                             const float pr = mk ? 0.f : __expf(sv - lse_s[q]);
-                            const bool kp = !p.drop.thr || att_keep1(p.drop, att_drop_row(p, r, h, q < Sq ? q : 0) + keyl);
+                            const bool kp = !p.drop.thr || att_keep1(p.drop, att_drop_row(p.S, p.H, r, h, q < Sq ? q : 0) + keyl);
                             pv[e2 * 4 + e] = kp ? pr * p.drop.scale : 0.f;
                             dsv[e2 * 4 + e] = pr * ((kp ? dp[e] * p.drop.scale : 0.f) - D_s[q]) * p.scale;
                         }
@@ -677,7 +591,7 @@ __global__ void __launch_bounds__(ATT_THREADS, NKT <= 12 ? 3 : 1) attn_bwd_dkv_k
                         for (int e = 0; e < 4; ++e) {
                             const float pr = __builtin_amdgcn_exp2f(s[e] * sl2 - l4[e]);
                             const int q = qt * 16 + 4 * g + e;
-                            const bool kp = !p.drop.thr || att_keep1(p.drop, att_drop_row(p, r, h, q < Sq ? q : 0) + keyl);
+                            const bool kp = !p.drop.thr || att_keep1(p.drop, att_drop_row(p.S, p.H, r, h, q < Sq ? q : 0) + keyl);
                             pv[e2 * 4 + e] = kp ? pr * p.drop.scale : 0.f;
                             dsv[e2 * 4 + e] = pr * ((kp ? dp[e] * p.drop.scale : 0.f) - d4[e]) * p.scale;
                         }
@@ -754,7 +668,7 @@ __global__ void __launch_bounds__(ATT_THREADS, NKT <= 12 ? 3 : 2) attn_bwd_dq_ex
             D_q += __shfl_xor(D_q, 32, 64);
             if (p.Dws && g == 0 && qok) p.Dws[((size_t)r * p.H + h) * Sq + q] = D_q;
             const f32x4 nl4 = {-lall[t], -lall[t], -lall[t], -lall[t]}, nd4 = {-D_q, -D_q, -D_q, -D_q};
-            const unsigned long long drow = att_drop_row(p, r, h, qok ? q : 0);
+            const unsigned long long drow = att_drop_row(p.S, p.H, r, h, qok ? q : 0);
             f32x4 dq[4];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -837,7 +751,7 @@ __global__ void __launch_bounds__(ATT_THREADS, NKT <= 12 ? 3 : 2) attn_bwd_dkv_e
     const RowBase Qrow = att_row_base(Qs, lane), Grow = att_row_base(Gs, lane);
     const TrBase Qtr = att_tr_base(Qs, lane), Gtr = att_tr_base(Gs, lane);
     const int nw = (Sq + 31) / 32;                        // query-tile pairs holding any real query
-    const unsigned long long drow0 = att_drop_row(p, r, h, 0);   // dropout element index of (query 0, key 0) of this (row, head)
+    const unsigned long long drow0 = att_drop_row(p.S, p.H, r, h, 0);   // dropout element index of (query 0, key 0) of this (row, head)
     const int S4 = (S + 3) & ~3;
 #pragma unroll
     for (int t = 0; t < MAXKT; ++t) {
@@ -920,7 +834,6 @@ __global__ void __launch_bounds__(ATT_THREADS, NKT <= 12 ? 3 : 2) attn_bwd_fused
 #endif
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int SP = NKT * 16, MAXT = (NKT + 3) / 4, IT = SP * 8 / ATT_THREADS;
-    constexpr bool EARLY_TR = ATT_EARLY_TR && NKT <= 12;
     constexpr bool KEEP_KV = true;        // K/V fragments of all of this wave's key tiles stay in registers and are written to LDS for
                                           // the dQ phase (no second read); NKT = 16 has no registers for that and re-reads K, V
     bf16_t* As = (bf16_t*)smem;          // Q, then K
@@ -1010,11 +923,6 @@ __global__ void __launch_bounds__(ATT_THREADS, NKT <= 12 ? 3 : 2) attn_bwd_fused
                 for (int w = 0; w < nw; ++w) {
                     const int off = w * 32 * LDSROW;
                     float pv[8], dsv[8];
-                    bf16x8 gfr[4], qfr[4];       // dO^T / Q^T fragments of this query pair: read first, their latency sits under the softmax block
-                    if (EARLY_TR) {
-#pragma unroll
-                        for (int dt = 0; dt < 4; ++dt) { gfr[dt] = lds_tr8i(Btr.d[dt] + off, 0, 16); qfr[dt] = lds_tr8i(Atr.d[dt] + off, 0, 16); }
-                    }
 #pragma unroll
                     for (int e2 = 0; e2 < 2; ++e2) {
                         const int o2 = off + e2 * 16 * LDSROW;
@@ -1065,9 +973,9 @@ __global__ void __launch_bounds__(ATT_THREADS, NKT <= 12 ? 3 : 2) attn_bwd_fused
                     const bf16x8 pa = pack8(pv), da = pack8(dsv);
 #pragma unroll
                     for (int dt = 0; dt < 4; ++dt) {
-                        if (!EARLY_TR) { gfr[dt] = lds_tr8i(Btr.d[dt] + off, 0, 16); qfr[dt] = lds_tr8i(Atr.d[dt] + off, 0, 16); }
-                        dv[dt] = mfma16(gfr[dt], pa, dv[dt]);   // dV^T / dK^T: rows = head dims, cols = keys
-                        dk[dt] = mfma16(qfr[dt], da, dk[dt]);
+                        const bf16x8 gfr = lds_tr8i(Btr.d[dt] + off, 0, 16), qfr = lds_tr8i(Atr.d[dt] + off, 0, 16);   // dO^T / Q^T fragments of this query pair
+                        dv[dt] = mfma16(gfr, pa, dv[dt]);   // dV^T / dK^T: rows = head dims, cols = keys
+                        dk[dt] = mfma16(qfr, da, dk[dt]);
                     }
                 }
                 if (kok) {

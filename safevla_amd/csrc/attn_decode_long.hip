@@ -12,12 +12,12 @@
 //  * both passes walk only the set bits of that mask, DECL_U blocks per trip with all of a trip's loads issued before the first use: the cost follows the
 //    episode's length, not the window;
 //  * scores wait in LDS (4 KiB) between the passes instead of in registers.
+#include "attn_common.h"      // LOG2E / LN2
 #include "attn_decode_long.h"
 
 #define HD 64
 #define DECL_THREADS 256
 #define DECL_U 8             // blocks per trip: 8 x 16 bytes per thread in flight
-static constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
 
 struct DecLongArgs {
     const bf16_t *Q, *K, *V; long ld;

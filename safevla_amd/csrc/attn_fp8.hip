@@ -14,13 +14,11 @@
 // at block offset 8g are tokens {4g..4g+3, 16+4g..16+4g+3}: exactly the 8 reduction slots in which a lane group g holds two
 // consecutive 16x16 score tiles (its probabilities / dS), which therefore feed the next MFMA without any data movement.
 // Static power-of-two scales keep P (x256, in [0, 284]) and dS (raw units x 2^-13) inside e4m3 / e5m2 range.
-#include "common.h"
+#include "attn_common.h"      // dropout index and keep test, LOG2E / LN2
 
 typedef unsigned char u8;
 #define HD 64
 #define F8_THREADS 256
-#define LOG2E 1.4426950408889634f
-#define LN2 0.6931471805599453f
 #define E4M3_MAX 448.f
 #define E5M2_TARGET 16384.f        // dO slices are scaled to amax = 2^14 (e5m2 max is 57344; its 2 mantissa bits do not care)
 #define P_SCALE 256.f
@@ -41,20 +39,12 @@ struct Fp8Args {
     DropCfg drop;
 };
 
-__device__ __forceinline__ unsigned long long att_drop_row8(int S, int H, int r, int h, int q) {
-    return ((unsigned long long)((size_t)r * H + h) * S + q) * (unsigned long long)((S + 3) & ~3);
-}
-__device__ __forceinline__ bool att_keep1_8(const DropCfg& c, unsigned long long e) {
-    const unsigned x = drop_bits(c.key, e >> 1);
-    return ((e & 1) ? (x >> 16) : (x & 0xffffu)) >= c.thr;
-}
-
 // Incremental dropout hash (the bf16 kernels' scheme, attn.hip): the element-pair index P = P0 + q*(S4/2) + (key >> 1) is linear in (query, key),
 // so lo(P) * C1 = lane constant + wave-uniform term; hi(P) is constant unless lo(P0) is within 2^16 of wrapping (then: the generic hash).
 struct F8Drop { unsigned a0, hb; bool wrap; unsigned long long p0; };
 __device__ __forceinline__ F8Drop f8_drop_head(const DropCfg& c, int S, int H, int r, int h) {
     F8Drop d;
-    d.p0 = att_drop_row8(S, H, r, h, 0) >> 1;
+    d.p0 = att_drop_row(S, H, r, h, 0) >> 1;
     d.a0 = (unsigned)d.p0 * 0x9E3779B1u;
     d.hb = ((unsigned)(d.p0 >> 32) * 0x85EBCA77u) ^ c.key;
     d.wrap = (unsigned)d.p0 > 0xFFFF0000u;
@@ -259,7 +249,7 @@ __global__ void __launch_bounds__(F8_THREADS, 2) attn_fp8_fwd_kernel(Fp8Args p) 
             f32x4 o[4];
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
-            const unsigned long long drow = DROP ? att_drop_row8(S, p.H, r, h, qok ? q : 0) : 0ull;
+            const unsigned long long drow = DROP ? att_drop_row(S, p.H, r, h, qok ? q : 0) : 0ull;
             const unsigned al_q = DROP ? dh.a0 + (unsigned)((qok ? q : 0) * hS + 2 * g) * 0x9E3779B1u : 0u;      // lane part: query row + first key pair of its 4 keys
 #pragma unroll
             for (int u = 0; u < NKT / 2; ++u) {
@@ -335,7 +325,7 @@ __global__ void __launch_bounds__(F8_THREADS, 2) attn_fp8_bwd_kernel(Fp8Args p) 
     const F8Row rr = f8_row_off(lane);
     const int tr_off = ql * (SP + 16) + 8 * g;
     const f32x4 c14 = {c1, c1, c1, c1};
-    const unsigned long long drow0 = DROP ? att_drop_row8(S, p.H, r, h, 0) : 0ull;
+    const unsigned long long drow0 = DROP ? att_drop_row(S, p.H, r, h, 0) : 0ull;
     const int S4 = (S + 3) & ~3, hS = S4 >> 1;
     F8Drop dh{};
     if (DROP) dh = f8_drop_head(p.drop, S, p.H, r, h);
@@ -383,7 +373,7 @@ __global__ void __launch_bounds__(F8_THREADS, 2) attn_fp8_bwd_kernel(Fp8Args p) 
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 const int q = (2 * w + e2) * 16 + 4 * g + e;
-                                keep |= att_keep1_8(p.drop, drow0 + (unsigned)((q < S ? q : 0) * S4 + keyl)) ? (1u << e) : 0u;
+                                keep |= att_keep1(p.drop, drow0 + (unsigned)((q < S ? q : 0) * S4 + keyl)) ? (1u << e) : 0u;
                             }
                         }
                     }

@@ -12,11 +12,11 @@
 //
 // LDS image of one [SP, 96] head slice.  A row is 192 B = twelve 16-byte chunks, so the 8-chunk XOR of attn.hip does not carry over.
 // The slice is stored as TWO PANELS, each with a power-of-two row and its own swizzle:
-//   panel A: columns  0..63, [SP][64], 128-byte rows, chunk c -> c ^ fA(row), fA = att_swz of attn.hip (x = (row >> 1) & 7 -> 0,2,4,6,5,7,1,3)
+//   panel A: columns  0..63, [SP][64], 128-byte rows, chunk c -> c ^ fA(row), fA = att_swz of attn_common.h (x = (row >> 1) & 7 -> 0,2,4,6,5,7,1,3)
 //   panel B: columns 64..95, [SP][32],  64-byte rows, chunk c -> c ^ fB(row), fB(y = (row >> 2) & 3) = 0,2,3,1
 // 192 B per row, no padding: K + V are 72 KiB for S <= 192 (two workgroups per CU in 160 KiB) and 96 KiB for S <= 256 (one).
 // Banks are (byte address / 4) mod 64 for every read used here, i.e. a 256-byte bank row holds two rows of panel A or four of panel B.
-// What each access pattern asks of panel B (panel A: the derivation at att_swz in attn.hip):
+// What each access pattern asks of panel B (panel A: the derivation at att_swz in attn_common.h):
 //  * ds_read_b128 row fragments of the third k-step (row = lane & 15, chunk = lane >> 4): the hardware serves the 16-lane groups
 //    {0-3,12-15,20-27}, {4-11,16-19,28-31}, ...: rows {0-3,12-15} on chunk c together with rows {4-11} on chunk c ^ 1.  Rows j, j+4,
 //    j+8, j+12 share the 64-byte bank quarter j & 3, so their four 16-byte slots must differ:
@@ -26,14 +26,11 @@
 //  * staging stores (ds_write_b128, 8 lanes = two whole rows = 128 contiguous bytes): any fB.
 // fB = 0,2,3,1 satisfies all three (1 ^ fB(1) = 3, 1 ^ fB(2) = 2); both panels are conflict-free for both kinds of read under the
 // bank rule above.
+#include "attn_common.h"      // dropout index, panel A's swizzle (att_swz), fragment helpers
 #include "attn_hd96.h"
 
 #define HD96 96
 #define A96_THREADS 256
-#define LOG2E 1.4426950408889634f
-#define LN2 0.6931471805599453f
-
-enum { A96_MASK_NONE = 0, A96_MASK_BLOCK_CAUSAL = 1 };
 
 struct Attn96Args {
     const bf16_t *Q, *K, *V; long ld;     // token row stride (elements) of the k/v tensors
@@ -52,17 +49,6 @@ struct Attn96Args {
     DropCfg drop;
 };
 
-__device__ __forceinline__ unsigned long long a96_drop_row(const Attn96Args& p, int r, int h, int q) {
-    return ((unsigned long long)((size_t)r * p.H + h) * p.S + q) * (unsigned long long)((p.S + 3) & ~3);
-}
-__device__ __forceinline__ bool a96_keep1(const DropCfg& c, unsigned long long e) {
-    const unsigned x = drop_bits(c.key, e >> 1);
-    return ((e & 1) ? (x >> 16) : (x & 0xffffu)) >= c.thr;
-}
-__device__ __forceinline__ int a96_swz_a(int row) {
-    const int x = (row >> 1) & 7;
-    return (((x + ((x >> 2) << 1)) & 3) << 1) | (x >> 2);
-}
 __device__ __forceinline__ int a96_swz_b(int row) { return (0x78 >> (((row >> 2) & 3) << 1)) & 3; }      // 0,2,3,1
 
 // One head slice in LDS: panel A at the base, panel B behind it.  Tile rows are multiples of 16 and both swizzles have period 16, so the
@@ -76,14 +62,14 @@ template <int SP> struct A96Img {
 struct Row96 { const bf16_t* k[3]; };
 template <int SP>
 __device__ __forceinline__ Row96 a96_row_base(const bf16_t* img, int lane) {
-    const int ql = lane & 15, g = lane >> 4, fa = a96_swz_a(ql), fb = a96_swz_b(ql);
+    const int ql = lane & 15, g = lane >> 4, fa = att_swz(ql), fb = a96_swz_b(ql);
     return Row96{{img + ql * 64 + ((g ^ fa) << 3), img + ql * 64 + (((g + 4) ^ fa) << 3), img + A96Img<SP>::PANEL_B + ql * 32 + ((g ^ fb) << 3)}};
 }
 struct Tr96 { const bf16_t* d[6]; };
 template <int SP>
 __device__ __forceinline__ Tr96 a96_tr_base(const bf16_t* img, int lane) {
     const int ql = lane & 15, g = lane >> 4;
-    const int row = 4 * g + (ql >> 2), fa = a96_swz_a(row), fb = a96_swz_b(row);
+    const int row = 4 * g + (ql >> 2), fa = att_swz(row), fb = a96_swz_b(row);
     const int hi = (ql & 3) >> 1, sub = 4 * (ql & 1);
     Tr96 t;
 #pragma unroll
@@ -121,24 +107,9 @@ __device__ __forceinline__ f32x4 a96_dot3(const Row96& b, int tile_row0, const b
     acc = mfma16(a96_row8<2>(b, tile_row0), frag[2], acc);
     return acc;
 }
-__device__ __forceinline__ bf16x8 a96_pack8(const float (&v)[8]) {
-    u32x4 w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = pack_bf2(v[2 * i], v[2 * i + 1]);
-    return __builtin_bit_cast(bf16x8, w);
-}
-__device__ __forceinline__ bf16x8 a96_gld8(const bf16_t* p, bool ok) {
-    return ok ? *(const bf16x8*)p : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-}
-__device__ __forceinline__ float a96_dot8(bf16x8 a, bf16x8 b) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += bf2f((bf16_t)a[i]) * bf2f((bf16_t)b[i]);
-    return s;
-}
 // this lane's three k-step fragments of one 96-wide token row (columns 8g, 32 + 8g, 64 + 8g): zero when !ok
 __device__ __forceinline__ void a96_gld_row(bf16x8 (&dst)[3], const bf16_t* row_g, bool ok) {
-    dst[0] = a96_gld8(row_g, ok); dst[1] = a96_gld8(row_g + 32, ok); dst[2] = a96_gld8(row_g + 64, ok);
+    dst[0] = gld8(row_g, ok); dst[1] = gld8(row_g + 32, ok); dst[2] = gld8(row_g + 64, ok);
 }
 // 8-byte stores of the six output tiles: acc[dt][e] = column dt*16 + 4g + e of this lane's token row
 __device__ __forceinline__ void a96_store_row(bf16_t* row_g4, const f32x4 (&acc)[6], float mul) {
@@ -170,20 +141,13 @@ __device__ __forceinline__ void a96_stage(bf16_t* img, const bf16_t* src, long l
 #pragma unroll
     for (int i = 0; i < ITA; ++i) {
         const int q = tid + i * A96_THREADS, row = q >> 3;
-        *(u32x4*)(img + row * 64 + (((q & 7) ^ a96_swz_a(row)) << 3)) = wa[i];
+        *(u32x4*)(img + row * 64 + (((q & 7) ^ att_swz(row)) << 3)) = wa[i];
     }
 #pragma unroll
     for (int i = 0; i < ITB; ++i) {
         const int q = tid + i * A96_THREADS, row = q >> 2;
         *(u32x4*)(img + A96Img<SP>::PANEL_B + row * 32 + (((q & 3) ^ a96_swz_b(row)) << 3)) = wb[i];
     }
-}
-
-__device__ __forceinline__ bool a96_masked(const Attn96Args& p, int q, int key, const int* traj_s, const unsigned char* kv_s) {
-    if (key >= p.S) return true;
-    if (p.mask_mode == A96_MASK_BLOCK_CAUSAL && (key > q || traj_s[key] != traj_s[q])) return true;
-    if (kv_s && !kv_s[key]) return true;
-    return false;
 }
 
 // ================================================================================================ forward
@@ -246,7 +210,7 @@ __global__ void __launch_bounds__(A96_THREADS, NKT <= 12 ? 2 : 1) attn96_fwd_ker
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float s = a[e] * sl2;
-                    if (a96_masked(p, q < Sq ? q : 0, kt * 16 + 4 * g + e, traj_s, kvp)) s = -INFINITY;
+                    if (att_masked(p, q < Sq ? q : 0, kt * 16 + 4 * g + e, traj_s, kvp)) s = -INFINITY;
                     sc[kt][e] = s;
                     mx = fmaxf(mx, s);
                 }
@@ -272,7 +236,7 @@ __global__ void __launch_bounds__(A96_THREADS, NKT <= 12 ? 2 : 1) attn96_fwd_ker
         lsum += __shfl_xor(lsum, 16, 64);
         lsum += __shfl_xor(lsum, 32, 64);
         if (p.drop.thr) {      // dropout on the normalised probabilities: zero here, 1/(1-p) folded into the final scale
-            const unsigned long long rb = a96_drop_row(p, r, h, q < Sq ? q : 0);
+            const unsigned long long rb = att_drop_row(p.S, p.H, r, h, q < Sq ? q : 0);
 #pragma unroll
             for (int kt = 0; kt < NKT; ++kt) {
                 const unsigned keep = drop_keep4(p.drop, rb + kt * 16 + 4 * g);
@@ -288,7 +252,7 @@ __global__ void __launch_bounds__(A96_THREADS, NKT <= 12 ? 2 : 1) attn96_fwd_ker
             if (u * 32 < S) {
                 const float pv[8] = {sc[2 * u][0], sc[2 * u][1], sc[2 * u][2], sc[2 * u][3],
                                      sc[2 * u + 1][0], sc[2 * u + 1][1], sc[2 * u + 1][2], sc[2 * u + 1][3]};
-                a96_mma6(o, Vtr, u, a96_pack8(pv));      // O^T: rows = head dims, cols = queries
+                a96_mma6(o, Vtr, u, pack8(pv));      // O^T: rows = head dims, cols = queries
             }
         }
         const float inv = lsum > 0.f ? p.drop.scale / lsum : 0.f;
@@ -344,7 +308,7 @@ __global__ void __launch_bounds__(A96_THREADS, NKT <= 12 ? 2 : 1) attn96_bwd_dq_
         a96_gld_row(qd, p.Q + tok * p.ldq + h * HD96 + 8 * g, qok);
         a96_gld_row(gd, p.dO + tok * p.lddo + h * HD96 + 8 * g, qok);
         a96_gld_row(of, p.O + tok * p.ldo + h * HD96 + 8 * g, qok);
-        dd = a96_dot8(gd[0], of[0]) + a96_dot8(gd[1], of[1]) + a96_dot8(gd[2], of[2]);
+        dd = dot8(gd[0], of[0]) + dot8(gd[1], of[1]) + dot8(gd[2], of[2]);
         ll = qok ? p.LSE[((size_t)r * p.H + h) * Sq + q] : INFINITY;
     };
     load_q(0, qbuf[0], gbuf[0], dbuf[0], lbuf[0]);
@@ -376,12 +340,12 @@ __global__ void __launch_bounds__(A96_THREADS, NKT <= 12 ? 2 : 1) attn96_bwd_dq_
                     const f32x4 s = a96_dot3(Krow, kt * 16, qf, f32x4{0.f, 0.f, 0.f, 0.f});
                     const f32x4 dp = a96_dot3(Vrow, kt * 16, gf, f32x4{0.f, 0.f, 0.f, 0.f});
                     // dP = keep/(1-p) * (dO V^T): the forward's keep-mask, regenerated
-                    const unsigned dkeep = p.drop.thr ? drop_keep4(p.drop, a96_drop_row(p, r, h, qok ? q : 0) + kt * 16 + 4 * g) : 0xfu;
+                    const unsigned dkeep = p.drop.thr ? drop_keep4(p.drop, att_drop_row(p.S, p.H, r, h, qok ? q : 0) + kt * 16 + 4 * g) : 0xfu;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
                         float pr;
                         if constexpr (GENERIC) {
-                            const bool mk = !qok || a96_masked(p, qok ? q : 0, kt * 16 + 4 * g + e, traj_s, kvp);
+                            const bool mk = !qok || att_masked(p, qok ? q : 0, kt * 16 + 4 * g + e, traj_s, kvp);
                             pr = mk ? 0.f : __builtin_amdgcn_exp2f(s[e] * sl2 - lse2_q);
                         } else {
                             // no mask needed: padded keys have zero K rows (their dS never reaches dQ), padded queries have lse = +inf => P = 0
@@ -390,7 +354,7 @@ __global__ void __launch_bounds__(A96_THREADS, NKT <= 12 ? 2 : 1) attn96_bwd_dq_
                         dsv[e2 * 4 + e] = pr * (((dkeep >> e) & 1u ? dp[e] * p.drop.scale : 0.f) - D_q) * p.scale;
                     }
                 }
-                a96_mma6(dq, Ktr, u, a96_pack8(dsv));      // dQ^T: rows = head dims, cols = queries
+                a96_mma6(dq, Ktr, u, pack8(dsv));      // dQ^T: rows = head dims, cols = queries
             }
         }
         if (qok) a96_store_row(p.dQ + (qtok0 + q) * p.lddq + h * HD96 + 4 * g, dq, 1.f);
@@ -446,8 +410,8 @@ __global__ void __launch_bounds__(A96_THREADS, NKT <= 12 ? 2 : 1) attn96_bwd_dkv
             if (row < Sq) {
                 const bf16_t* gp = p.dO + (qtok0 + row) * p.lddo + h * HD96 + c;
                 const bf16_t* op = p.O + (qtok0 + row) * p.ldo + h * HD96 + c;
-                part[i] = a96_dot8(*(const bf16x8*)gp, *(const bf16x8*)op) + a96_dot8(*(const bf16x8*)(gp + 8), *(const bf16x8*)(op + 8)) +
-                          a96_dot8(*(const bf16x8*)(gp + 16), *(const bf16x8*)(op + 16));
+                part[i] = dot8(*(const bf16x8*)gp, *(const bf16x8*)op) + dot8(*(const bf16x8*)(gp + 8), *(const bf16x8*)(op + 8)) +
+                          dot8(*(const bf16x8*)(gp + 16), *(const bf16x8*)(op + 16));
             }
         }
 #pragma unroll
@@ -494,15 +458,15 @@ __global__ void __launch_bounds__(A96_THREADS, NKT <= 12 ? 2 : 1) attn96_bwd_dkv
                         const int q = qt * 16 + 4 * g + e;
                         float pr = __builtin_amdgcn_exp2f(s[e] * sl2 - l4[e]);
                         if constexpr (GENERIC) {
-                            if (q >= Sq || a96_masked(p, q < Sq ? q : 0, keyl, traj_s, kvp)) pr = 0.f;
+                            if (q >= Sq || att_masked(p, q < Sq ? q : 0, keyl, traj_s, kvp)) pr = 0.f;
                         }
-                        const bool kp = !p.drop.thr || a96_keep1(p.drop, a96_drop_row(p, r, h, q < Sq ? q : 0) + keyl);
+                        const bool kp = !p.drop.thr || att_keep1(p.drop, att_drop_row(p.S, p.H, r, h, q < Sq ? q : 0) + keyl);
                         pv[e2 * 4 + e] = kp ? pr * p.drop.scale : 0.f;
                         dsv[e2 * 4 + e] = pr * ((kp ? dp[e] * p.drop.scale : 0.f) - d4[e]) * p.scale;
                     }
                 }
-                a96_mma6(dv, Gtr, w, a96_pack8(pv));       // dV^T / dK^T: rows = head dims, cols = keys
-                a96_mma6(dk, Qtr, w, a96_pack8(dsv));
+                a96_mma6(dv, Gtr, w, pack8(pv));       // dV^T / dK^T: rows = head dims, cols = keys
+                a96_mma6(dk, Qtr, w, pack8(dsv));
             }
         }
         if (kok) {
@@ -526,7 +490,7 @@ static int a96_launch_fwd(const Attn96Args& p, int rows, hipStream_t st) {
         attr = true;
     }
     const dim3 grid(rows * p.H > 0 ? rows * p.H : 1);      // one workgroup per (row, head); rows, H >= 1 is checked by the caller
-    if (p.mask_mode != A96_MASK_NONE || p.kvalid) hipLaunchKernelGGL((attn96_fwd_kernel<NKT, true>), grid, dim3(A96_THREADS), lds, st, p);
+    if (p.mask_mode != MASK_NONE || p.kvalid) hipLaunchKernelGGL((attn96_fwd_kernel<NKT, true>), grid, dim3(A96_THREADS), lds, st, p);
     else hipLaunchKernelGGL((attn96_fwd_kernel<NKT, false>), grid, dim3(A96_THREADS), lds, st, p);
     return svla_launch_status();
 }
@@ -542,7 +506,7 @@ static int a96_launch_bwd(const Attn96Args& p, int rows, hipStream_t st) {
         attr = true;
     }
     const dim3 grid(rows * p.H > 0 ? rows * p.H : 1);
-    if (p.mask_mode != A96_MASK_NONE || p.kvalid) {
+    if (p.mask_mode != MASK_NONE || p.kvalid) {
         hipLaunchKernelGGL((attn96_bwd_dq_kernel<NKT, true>), grid, dim3(A96_THREADS), lds_q, st, p);
         hipLaunchKernelGGL((attn96_bwd_dkv_kernel<NKT, true>), grid, dim3(A96_THREADS), lds_kv, st, p);
     } else {
@@ -556,7 +520,7 @@ int attn96_fwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long ld
                       float scale, int mask_mode, const int* traj, const float* bias, const unsigned char* kvalid, int Sq, long ldq, int kv_rows,
                       const svla_dropout* drop, void* stream) {
     if (rows <= 0 || S <= 0 || S > 256 || bias || (ld % 8) || (ldo % 4) || H <= 0 || (kv_rows > 0 && kv_rows < S)) return SVLA_EINVAL;
-    if (mask_mode != A96_MASK_NONE && (mask_mode != A96_MASK_BLOCK_CAUSAL || !traj)) return SVLA_EINVAL;
+    if (mask_mode != MASK_NONE && (mask_mode != MASK_BLOCK_CAUSAL || !traj)) return SVLA_EINVAL;
     if (Sq < 0 || Sq > S || (Sq > 0 && (ldq % 8))) return SVLA_EINVAL;
     Attn96Args p{};
     p.Q = Q; p.K = K; p.V = V; p.ld = ld; p.O = O; p.ldo = ldo; p.LSE = LSE; p.traj = traj; p.kvalid = kvalid;
@@ -575,7 +539,7 @@ int attn96_bwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long ld
                       long lddo, bf16_t* dQ, bf16_t* dK, bf16_t* dV, long ldd, int rows, int S, int H, float scale, int mask_mode, const int* traj,
                       const float* bias, const unsigned char* kvalid, int Sq, long ldq, long lddq, float* D_ws, const svla_dropout* drop, void* stream) {
     if (rows <= 0 || S <= 0 || S > 256 || bias || (ld % 8) || (ldo % 8) || (lddo % 8) || (ldd % 4) || H <= 0) return SVLA_EINVAL;
-    if (mask_mode != A96_MASK_NONE && (mask_mode != A96_MASK_BLOCK_CAUSAL || !traj)) return SVLA_EINVAL;
+    if (mask_mode != MASK_NONE && (mask_mode != MASK_BLOCK_CAUSAL || !traj)) return SVLA_EINVAL;
     if (Sq < 0 || Sq > S || (Sq > 0 && ((ldq % 8) || (lddq % 4)))) return SVLA_EINVAL;
     Attn96Args p{};
     p.Sq = Sq > 0 ? Sq : S; p.ldq = Sq > 0 ? ldq : ld; p.lddq = Sq > 0 ? lddq : ldd; p.kv_rows = S;

@@ -2,7 +2,7 @@
 // The llama decoder attends over the time axis of a rollout or of a whole episode (block-causal on the trajectory ids, key padding, dropout); the
 // forward (attn.hip: launch_fwd<18|28|32>) and the KV cache of the acting path already reach 512 steps, this file is the training half.
 //
-// Same arithmetic contract as the S <= 256 kernel pair of attn.hip (whose header describes the swapped QK^T layout and the LDS swizzle): P is recomputed
+// Same arithmetic contract as the S <= 256 kernel pair of attn.hip (whose header describes the swapped QK^T layout; the LDS swizzle: attn_common.h): P is recomputed
 // from the saved natural-log LSE, D = rowsum(dO * O), probabilities and dS are rounded to bf16 before the second product, the dropout element index is
 // ((r*H + h)*S + q) * SP4 + k (include/svla.h: svla_dropout), dQ / dK / dV are bf16 and written once each by plain stores (no atomics: bitwise repeatable).
 //   dQ    kernel: waves own query tiles, K and V resident in LDS:   dQ = dS.K
@@ -15,15 +15,13 @@
 //   * with the block-causal mask the tile pairs that lie wholly above the diagonal are skipped (wave-uniform loop bounds): half the work of a decoder layer;
 //   * the next tile's Q / dO (K / V) fragments are fetched from global memory while the current tile is computed.
 // Not built here: the T5 bias (the only biased attention is frozen and has no backward), S > 512, head_dim 96.
+#include "attn_common.h"      // dropout index, LDS swizzle (att_swz) and lane bases, fragment helpers
 #include "attn_long.h"
 
 #define AL_HD 64
-#define AL_ROW 64           // LDS row = 128 B, 16-byte chunks XOR-swizzled as in attn.hip (att_swz)
+#define AL_ROW LDSROW       // LDS row = 128 B, 16-byte chunks XOR-swizzled (att_swz)
 #define AL_NW 8
 #define AL_THREADS (AL_NW * 64)
-#define AL_LOG2E 1.4426950408889634f
-
-enum { AL_MASK_NONE = 0, AL_MASK_BLOCK_CAUSAL = 1 };
 
 struct AttnLongArgs {
     const bf16_t *Q, *K, *V; long ld;     // token row stride (elements) of the k/v tensors
@@ -40,56 +38,6 @@ struct AttnLongArgs {
     DropCfg drop;
 };
 
-__device__ __forceinline__ unsigned long long al_drop_row(const AttnLongArgs& p, int r, int h, int q) {
-    return ((unsigned long long)((size_t)r * p.H + h) * p.S + q) * (unsigned long long)((p.S + 3) & ~3);
-}
-__device__ __forceinline__ bool al_keep1(const DropCfg& c, unsigned long long e) {
-    const unsigned x = drop_bits(c.key, e >> 1);
-    return ((e & 1) ? (x >> 16) : (x & 0xffffu)) >= c.thr;
-}
-// physical 16-byte chunk of logical chunk c in row r: c ^ f((r >> 1) & 7), f = 0,2,4,6,5,7,1,3 (derivation: att_swz in attn.hip)
-__device__ __forceinline__ int al_swz(int row) {
-    const int x = (row >> 1) & 7;
-    return (((x + ((x >> 2) << 1)) & 3) << 1) | (x >> 2);
-}
-// Lane bases of the two access patterns (tile rows are multiples of 16, so the swizzle term depends on the lane only):
-//   row fragment : row = tile + (lane & 15), logical chunk (lane >> 4) [+4 for columns 32..63]
-//   transposed   : row = tile + 4 (lane >> 4) + ((lane & 15) >> 2), columns dt*16 + 4 ((lane & 15) & 3) .. +3
-struct AlRow { const bf16_t* lo; const bf16_t* hi; };
-__device__ __forceinline__ AlRow al_row_base(const bf16_t* img, int lane) {
-    const int ql = lane & 15, g = lane >> 4, f = al_swz(ql);
-    return AlRow{img + ql * AL_ROW + ((g ^ f) << 3), img + ql * AL_ROW + (((g + 4) ^ f) << 3)};
-}
-struct AlTr { const bf16_t* d[4]; };
-__device__ __forceinline__ AlTr al_tr_base(const bf16_t* img, int lane) {
-    const int ql = lane & 15, g = lane >> 4;
-    const int row = 4 * g + (ql >> 2), f = al_swz(row);
-    AlTr t;
-#pragma unroll
-    for (int dt = 0; dt < 4; ++dt) t.d[dt] = img + row * AL_ROW + (((2 * dt + ((ql & 3) >> 1)) ^ f) << 3) + 4 * (ql & 1);
-    return t;
-}
-__device__ __forceinline__ bf16x8 al_row8(const bf16_t* lane_base, int tile_row0) { return *(const bf16x8*)(lane_base + tile_row0 * AL_ROW); }
-// B/A-operand gather: 8 reduction slots = rows {r0 + 4g + 0..3, r0 + 16 + 4g + 0..3}, column dt*16 + (lane & 15)
-__device__ __forceinline__ bf16x8 al_tr8(const bf16_t* lane_base_dt, int r0) {
-    const bf16x4 lo = lds_tr16_b64(lane_base_dt + r0 * AL_ROW);
-    const bf16x4 hi = lds_tr16_b64(lane_base_dt + (r0 + 16) * AL_ROW);
-    return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-}
-__device__ __forceinline__ bf16x8 al_pack8(const float (&v)[8]) {
-    u32x4 w;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) w[i] = pack_bf2(v[2 * i], v[2 * i + 1]);
-    return __builtin_bit_cast(bf16x8, w);
-}
-__device__ __forceinline__ bf16x8 al_gld8(const bf16_t* p, bool ok) { return ok ? *(const bf16x8*)p : bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; }
-__device__ __forceinline__ float al_dot8(bf16x8 a, bf16x8 b) {
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) s += bf2f((bf16_t)a[i]) * bf2f((bf16_t)b[i]);
-    return s;
-}
-
 // stage an [nrows, 64] head slice into SP LDS rows (zero-filled from nrows on): four 16-byte loads per thread in flight before the first LDS store
 __device__ __forceinline__ void al_stage(bf16_t* dst, const bf16_t* src, long ld, int nrows, int SP, int tid) {
     const int nchunk = SP * 8;
@@ -104,7 +52,7 @@ __device__ __forceinline__ void al_stage(bf16_t* dst, const bf16_t* src, long ld
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int q = q0 + i * AL_THREADS, row = q >> 3;
-            if (q < nchunk) *(u32x4*)(dst + row * AL_ROW + (((q & 7) ^ al_swz(row)) << 3)) = w[i];
+            if (q < nchunk) *(u32x4*)(dst + row * AL_ROW + (((q & 7) ^ att_swz(row)) << 3)) = w[i];
         }
     }
 }
@@ -140,9 +88,9 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dq_kernel(AttnLongAr
         const bf16_t* gp = p.dO + row * p.lddo + h * AL_HD + 8 * g;
         const bf16_t* op = p.O + row * p.ldo + h * AL_HD + 8 * g;
         AlQFrag f;
-        f.q0 = al_gld8(qp, qok); f.q1 = al_gld8(qp + 32, qok);
-        f.g0 = al_gld8(gp, qok); f.g1 = al_gld8(gp + 32, qok);
-        f.d = al_dot8(f.g0, al_gld8(op, qok)) + al_dot8(f.g1, al_gld8(op + 32, qok));
+        f.q0 = gld8(qp, qok); f.q1 = gld8(qp + 32, qok);
+        f.g0 = gld8(gp, qok); f.g1 = gld8(gp + 32, qok);
+        f.d = dot8(f.g0, gld8(op, qok)) + dot8(f.g1, gld8(op + 32, qok));
         f.lse = qok ? p.LSE[((size_t)r * p.H + h) * Sq + q] : INFINITY;      // +inf => P = 0 for padded queries
         return f;
     };
@@ -154,10 +102,10 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dq_kernel(AttnLongAr
         ((unsigned char*)kv_s)[i] = i < S ? (p.kvalid ? (p.kvalid[tok0 + i] ? 1 : 0) : 1) : 0;
     }
     __syncthreads();
-    const bool causal = p.mask_mode == AL_MASK_BLOCK_CAUSAL;
-    const AlRow Krow = al_row_base(Ks, lane), Vrow = al_row_base(Vs, lane);
-    const AlTr Ktr = al_tr_base(Ks, lane);
-    const float sl2 = p.scale * AL_LOG2E;
+    const bool causal = p.mask_mode == MASK_BLOCK_CAUSAL;
+    const RowBase Krow = att_row_base(Ks, lane), Vrow = att_row_base(Vs, lane);
+    const TrBase Ktr = att_tr_base(Ks, lane);
+    const float sl2 = p.scale * LOG2E;
     for (int qt = wid; qt < ntile; qt += AL_NW) {
         const AlQFrag cur = nxt;
         if (qt + AL_NW < ntile) nxt = load_q(qt + AL_NW);
@@ -166,9 +114,9 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dq_kernel(AttnLongAr
         float D_q = cur.d;
         D_q += __shfl_xor(D_q, 16, 64);
         D_q += __shfl_xor(D_q, 32, 64);
-        const float lse_q = cur.lse, lse2_q = cur.lse * AL_LOG2E;
+        const float lse_q = cur.lse, lse2_q = cur.lse * LOG2E;
         const int tq = MASKED ? traj_s[qok ? q : 0] : 0;
-        const unsigned long long rb = p.drop.thr ? al_drop_row(p, r, h, qok ? q : 0) : 0ull;
+        const unsigned long long rb = p.drop.thr ? att_drop_row(p.S, p.H, r, h, qok ? q : 0) : 0ull;
         f32x4 dq[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -180,10 +128,10 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dq_kernel(AttnLongAr
             for (int e2 = 0; e2 < 2; ++e2) {
                 const int k0 = 32 * u + 16 * e2;
                 f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-                s = mfma16(al_row8(Krow.lo, k0), cur.q0, s);
-                s = mfma16(al_row8(Krow.hi, k0), cur.q1, s);
-                dp = mfma16(al_row8(Vrow.lo, k0), cur.g0, dp);
-                dp = mfma16(al_row8(Vrow.hi, k0), cur.g1, dp);
+                s = mfma16(lds_row8i(Krow.lo, k0), cur.q0, s);
+                s = mfma16(lds_row8i(Krow.hi, k0), cur.q1, s);
+                dp = mfma16(lds_row8i(Vrow.lo, k0), cur.g0, dp);
+                dp = mfma16(lds_row8i(Vrow.hi, k0), cur.g1, dp);
                 // s[e], dp[e]: key k0 + 4g + e, query q.  dP = keep/(1-p) * (dO V^T): the forward's keep-mask, regenerated
                 const unsigned dkeep = p.drop.thr ? drop_keep4(p.drop, rb + k0 + 4 * g) : 0xfu;
                 if constexpr (MASKED) {
@@ -203,9 +151,9 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dq_kernel(AttnLongAr
                         dsv[e2 * 4 + e] = __builtin_amdgcn_exp2f(s[e] * sl2 - lse2_q) * (((dkeep >> e) & 1u ? dp[e] * p.drop.scale : 0.f) - D_q) * p.scale;
                 }
             }
-            const bf16x8 da = al_pack8(dsv);
+            const bf16x8 da = pack8(dsv);
 #pragma unroll
-            for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma16(al_tr8(Ktr.d[dt], 32 * u), da, dq[dt]);      // dQ^T: rows = head dims, cols = queries
+            for (int dt = 0; dt < 4; ++dt) dq[dt] = mfma16(lds_tr8i(Ktr.d[dt], 32 * u, 32 * u + 16), da, dq[dt]);      // dQ^T: rows = head dims, cols = queries
         }
         if (qok) {
 #pragma unroll
@@ -243,8 +191,8 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dkv_kernel(AttnLongA
         const bf16_t* kp = p.K + (tok0 + (kok ? keyl : 0)) * p.ld + h * AL_HD + 8 * g;
         const bf16_t* vp = p.V + (tok0 + (kok ? keyl : 0)) * p.ld + h * AL_HD + 8 * g;
         AlKVFrag f;
-        f.k0 = al_gld8(kp, kok); f.k1 = al_gld8(kp + 32, kok);
-        f.v0 = al_gld8(vp, kok); f.v1 = al_gld8(vp + 32, kok);
+        f.k0 = gld8(kp, kok); f.k1 = gld8(kp + 32, kok);
+        f.v0 = gld8(vp, kok); f.v1 = gld8(vp + 32, kok);
         return f;
     };
     AlKVFrag nxt = load_kv(wid);      // in flight across the staging barrier
@@ -253,7 +201,7 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dkv_kernel(AttnLongA
     for (int i = tid; i < SP; i += AL_THREADS) {
         traj_s[i] = (p.traj && i < S) ? p.traj[tok0 + i] : -1;
         kv_s[i] = i < S ? (p.kvalid ? (p.kvalid[tok0 + i] ? 1 : 0) : 1) : 0;
-        lse_s[i] = i < Sq ? p.LSE[((size_t)r * p.H + h) * Sq + i] * (MASKED ? 1.f : AL_LOG2E) : INFINITY;      // +inf => P = 0 for padded queries
+        lse_s[i] = i < Sq ? p.LSE[((size_t)r * p.H + h) * Sq + i] * (MASKED ? 1.f : LOG2E) : INFINITY;      // +inf => P = 0 for padded queries
     }
     // D[q] = sum_d dO[q,d] * O[q,d]: 4 lanes per row (16 columns each); SP * 4 is a multiple of 128, so a wave is wholly inside or outside the loop
     for (int i = tid; i < SP * 4; i += AL_THREADS) {
@@ -262,17 +210,17 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dkv_kernel(AttnLongA
         if (row < Sq) {
             const bf16_t* gp = p.dO + (qtok0 + row) * p.lddo + h * AL_HD + c;
             const bf16_t* op = p.O + (qtok0 + row) * p.ldo + h * AL_HD + c;
-            v = al_dot8(*(const bf16x8*)gp, *(const bf16x8*)op) + al_dot8(*(const bf16x8*)(gp + 8), *(const bf16x8*)(op + 8));
+            v = dot8(*(const bf16x8*)gp, *(const bf16x8*)op) + dot8(*(const bf16x8*)(gp + 8), *(const bf16x8*)(op + 8));
         }
         v += __shfl_xor(v, 1, 64);
         v += __shfl_xor(v, 2, 64);
         if ((i & 3) == 0) D_s[row] = v;
     }
     __syncthreads();
-    const bool causal = p.mask_mode == AL_MASK_BLOCK_CAUSAL;
-    const AlRow Qrow = al_row_base(Qs, lane), Grow = al_row_base(Gs, lane);
-    const AlTr Qtr = al_tr_base(Qs, lane), Gtr = al_tr_base(Gs, lane);
-    const float sl2 = p.scale * AL_LOG2E;
+    const bool causal = p.mask_mode == MASK_BLOCK_CAUSAL;
+    const RowBase Qrow = att_row_base(Qs, lane), Grow = att_row_base(Gs, lane);
+    const TrBase Qtr = att_tr_base(Qs, lane), Gtr = att_tr_base(Gs, lane);
+    const float sl2 = p.scale * LOG2E;
     const unsigned SP4 = (unsigned)((S + 3) & ~3);
     const int nw = (Sq + 31) >> 5;      // query tile pairs that hold a query (<= SP / 32)
     for (int kt = wid; kt < ntile; kt += AL_NW) {
@@ -282,7 +230,7 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dkv_kernel(AttnLongA
         const bool kok = keyl < S;
         const int tk = traj_s[keyl];
         const bool kvis = kok && kv_s[keyl];
-        const unsigned long long eb = p.drop.thr ? al_drop_row(p, r, h, 0) + keyl : 0ull;      // element index of (query 0, this key); query q: + q * SP4 < 2^18
+        const unsigned long long eb = p.drop.thr ? att_drop_row(p.S, p.H, r, h, 0) + keyl : 0ull;      // element index of (query 0, this key); query q: + q * SP4 < 2^18
         f32x4 dk[4], dv[4];
 #pragma unroll
         for (int dt = 0; dt < 4; ++dt) { dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f}; }
@@ -293,10 +241,10 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dkv_kernel(AttnLongA
             for (int e2 = 0; e2 < 2; ++e2) {
                 const int q0 = 32 * w + 16 * e2;
                 f32x4 s = {0.f, 0.f, 0.f, 0.f}, dp = {0.f, 0.f, 0.f, 0.f};
-                s = mfma16(al_row8(Qrow.lo, q0), cur.k0, s);
-                s = mfma16(al_row8(Qrow.hi, q0), cur.k1, s);
-                dp = mfma16(al_row8(Grow.lo, q0), cur.v0, dp);
-                dp = mfma16(al_row8(Grow.hi, q0), cur.v1, dp);
+                s = mfma16(lds_row8i(Qrow.lo, q0), cur.k0, s);
+                s = mfma16(lds_row8i(Qrow.hi, q0), cur.k1, s);
+                dp = mfma16(lds_row8i(Grow.lo, q0), cur.v0, dp);
+                dp = mfma16(lds_row8i(Grow.hi, q0), cur.v1, dp);
                 // s[e], dp[e]: query q0 + 4g + e, key keyl
                 const f32x4 l4 = *(const f32x4*)(lse_s + q0 + 4 * g), d4 = *(const f32x4*)(D_s + q0 + 4 * g);
                 int tqe[4] = {0, 0, 0, 0};
@@ -314,16 +262,16 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dkv_kernel(AttnLongA
                     } else {
                         pr = __builtin_amdgcn_exp2f(s[e] * sl2 - l4[e]);      // lse_s holds lse*log2e (+inf for padded queries); padded key columns are never stored
                     }
-                    const bool kp = !p.drop.thr || al_keep1(p.drop, eb + (unsigned)(q < Sq ? q : 0) * SP4);
+                    const bool kp = !p.drop.thr || att_keep1(p.drop, eb + (unsigned)(q < Sq ? q : 0) * SP4);
                     pv[e2 * 4 + e] = kp ? pr * p.drop.scale : 0.f;
                     dsv[e2 * 4 + e] = pr * ((kp ? dp[e] * p.drop.scale : 0.f) - d4[e]) * p.scale;
                 }
             }
-            const bf16x8 pa = al_pack8(pv), da = al_pack8(dsv);
+            const bf16x8 pa = pack8(pv), da = pack8(dsv);
 #pragma unroll
             for (int dt = 0; dt < 4; ++dt) {
-                dv[dt] = mfma16(al_tr8(Gtr.d[dt], 32 * w), pa, dv[dt]);      // dV^T / dK^T: rows = head dims, cols = keys
-                dk[dt] = mfma16(al_tr8(Qtr.d[dt], 32 * w), da, dk[dt]);
+                dv[dt] = mfma16(lds_tr8i(Gtr.d[dt], 32 * w, 32 * w + 16), pa, dv[dt]);      // dV^T / dK^T: rows = head dims, cols = keys
+                dk[dt] = mfma16(lds_tr8i(Qtr.d[dt], 32 * w, 32 * w + 16), da, dk[dt]);
             }
         }
         if (kok) {
@@ -344,8 +292,8 @@ int attn_long_bwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long
                          const float* bias, const unsigned char* kvalid, int Sq, long ldq, long lddq, float* D_ws, const svla_dropout* drop, void* stream) {
     (void)D_ws;      // the dK/dV kernel computes D itself (O is read once per (row, head) either way); accepted so that callers need not know the bucket
     if (rows <= 0 || S <= 256 || S > 512 || (ld % 8) || (lddo % 8) || (ldo % 8) || (ldd % 4) || H <= 0 || bias) return SVLA_EINVAL;
-    if (mask_mode != AL_MASK_NONE && mask_mode != AL_MASK_BLOCK_CAUSAL) return SVLA_EINVAL;
-    if (mask_mode == AL_MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
+    if (mask_mode != MASK_NONE && mask_mode != MASK_BLOCK_CAUSAL) return SVLA_EINVAL;
+    if (mask_mode == MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
     if (Sq < 0 || Sq > S || (Sq > 0 && ((ldq % 8) || (lddq % 4)))) return SVLA_EINVAL;
     AttnLongArgs p{};
     p.Sq = Sq > 0 ? Sq : S; p.ldq = Sq > 0 ? ldq : ld; p.lddq = Sq > 0 ? lddq : ldd;
@@ -362,7 +310,7 @@ int attn_long_bwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long
     }
     const int SP = (S + 31) & ~31;
     hipStream_t st = (hipStream_t)stream;
-    if (mask_mode != AL_MASK_NONE || kvalid) {
+    if (mask_mode != MASK_NONE || kvalid) {
         hipLaunchKernelGGL((attn_long_bwd_dq_kernel<true>), dim3(rows * H), dim3(AL_THREADS), al_lds_dq(SP), st, p);
         hipLaunchKernelGGL((attn_long_bwd_dkv_kernel<true>), dim3(rows * H), dim3(AL_THREADS), al_lds_dkv(SP), st, p);
     } else {

@@ -6,15 +6,12 @@ at most 256 registers (arch VGPRs + AGPRs) per lane, and the S <= 256 bucket (96
 argument of the same kernels (``DropCfg::thr``), so "with and without dropout" is one code object per (bucket, masked?) pair: the zero-scratch
 requirement of the no-dropout forward therefore holds for the dropout forward too."""
 import os
-import re
-import subprocess
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "safevla_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "--cuda-device-only", "-c"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers.kernel_resources import HIPCC, resources as _resources      # noqa: E402
 
 # mangled-name fragment -> max registers per lane (VGPRs + AGPRs); the values of this build (in the comments) plus about 5 % slack, capped at what the
 # bucket's occupancy allows.  VGPR spills and scratch are pinned at zero for every kernel of the file.
@@ -33,22 +30,6 @@ BUDGET = {
     "21attn96_bwd_dkv_kernelILi16ELb1E": 376,    # 256 + 96
 }
 FIELDS = ("VGPRs", "AGPRs", "VGPRs Spill", "SGPRs Spill", "ScratchSize [bytes/lane]")
-
-
-def _resources(src):
-    r = subprocess.run([HIPCC, *FLAGS, "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(?:\S+:\d+:\d+:\s+)?([A-Za-z][^:]*): (\d+)", line)
-        if m and cur is not None and m.group(1) in FIELDS:
-            cur[m.group(1)] = int(m.group(2))
-    return out
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")

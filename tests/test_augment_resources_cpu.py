@@ -5,37 +5,19 @@ The three kernels index no array dynamically (operation codes, factors and blur 
 scratch; their LDS is static: the staged chunk of the gray reduction, the jitter tile with its blur halo, the crop source rectangle plus the resized tile with its
 sharpness halo.  All three must keep at least four waves per SIMD (128 VGPRs): they are memory-bound streams that live on occupancy."""
 import os
-import re
-import subprocess
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "safevla_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "--cuda-device-only", "-c"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers.kernel_resources import HIPCC, resources as _resources      # noqa: E402
+
 # kernel -> (VGPRs at most, LDS bytes per block exactly)
 PINS = {
     "aug_gray_partials_kernel": (40, 2048 * 3 + 16 + 4 * 8),                                              # 38 VGPRs when this was written
     "aug_jitter_blur_kernel": (88, 24 * ((128 + 4) * 3 + 12) + 24 + 4),                                   # 80
     "aug_resize_post_sharp_kernel": (32, 20 * ((128 + 4) * 3 + 12) + 18 * ((128 + 2) * 3 + 2) + 20),      # 25
 }
-
-
-def _resources(src):
-    r = subprocess.run([HIPCC, *FLAGS, "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(?:\S+\s+)?(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]|LDS Size \[bytes/block\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return out
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")

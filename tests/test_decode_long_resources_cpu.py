@@ -5,32 +5,14 @@ The long-window kernel (csrc/attn_decode_long.hip, 512 < S <= 1024) keeps its sc
 would not fit: it and its grouped twin must not spill.  The existing kernel for S <= 512 (csrc/attn.hip: attn_decode_kernel) carries the 64-env policy step and
 must compile as it did before the long window was added: 50 VGPRs, no scratch, single-launch kernel and grouped twin alike."""
 import os
-import re
-import subprocess
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "safevla_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "--cuda-device-only", "-c"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers.kernel_resources import HIPCC, resources as _resources      # noqa: E402
+
 DECODE_VGPRS = 50           # attn_decode_kernel and its grouped twin before this kernel existed
-
-
-def _resources(src):
-    r = subprocess.run([HIPCC, *FLAGS, "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark:\s+(?:\S+\s+)?(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return out
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")

@@ -4,16 +4,13 @@ Round 6 found a 5.6 % regression of the whole update by an A/B against the previ
 __global__ functions (for the tower-grouped launches) made `attn_fwd_persist_kernel<12>` spill 109 VGPRs instead of 6 and run 2x slower, while every parity test stayed
 green.  This test pins what the compiler does with the kernels that carry the update: VGPR count (= occupancy) and spill counts from -Rpass-analysis=kernel-resource-usage."""
 import os
-import re
-import subprocess
+import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "safevla_amd", "csrc")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-mllvm", "-amdgpu-mfma-vgpr-form=1", "--cuda-device-only", "-c"]
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers.kernel_resources import HIPCC, resources as _resources      # noqa: E402
 
 # kernel-name fragment (mangled) -> (max VGPRs, max spilled VGPRs): the values of the round-6 build with a little slack; a change of schedule that needs more is a
 # decision to take with an A/B in hand (tools/ab_attn.py, bench.py against the previous tree), not something to discover in a profile a round later
@@ -37,22 +34,6 @@ BUDGET = {
         "15norm_bwd_kernelItLi512EE": (128, 4),
     },
 }
-
-
-def _resources(src):
-    r = subprocess.run([HIPCC, *FLAGS, "-I", os.path.join(ROOT, "include"), os.path.join(CSRC, src), "-o", os.devnull, "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True, cwd=CSRC)
-    assert r.returncode == 0, r.stderr[-3000:]
-    out, cur = {}, None
-    for line in r.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = out.setdefault(m.group(1), {})
-            continue
-        m = re.search(r"remark: [^ ]+ +(VGPRs|VGPRs Spill|SGPRs Spill|ScratchSize \[bytes/lane\]): (\d+)", line)
-        if m and cur is not None:
-            cur[m.group(1)] = int(m.group(2))
-    return out
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
