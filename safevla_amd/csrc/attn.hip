@@ -1113,13 +1113,8 @@ static int launch_fwd(const AttnArgs& p, int rows, hipStream_t st) {
     if constexpr (NKT == 12 || NKT == 16) {
         if (!generic && p.S > (NKT - 2) * 16) {
             const size_t ldsp = (size_t)2 * NKT * 16 * LDSROW * sizeof(bf16_t);
-            static int slots = 0;
-            if (!slots) {
-                int dev = 0, n_cu = 0;
-                HIP_CHECK_RET(hipGetDevice(&dev));
-                HIP_CHECK_RET(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-                slots = 2 * n_cu;              // 2 workgroups per CU
-            }
+            const int slots = 2 * svla_cu_count();      // 2 workgroups per CU
+            if (!slots) return (int)hipErrorInvalidDevice;
             const int nitems = rows * p.H;
             // (a tower group shares the two-workgroups-per-CU budget: the grouped launch carries one third of the slots per member)
             const int gslots = (slots / svla_group_size()) & ~7;
@@ -1148,49 +1143,36 @@ template <int NKT>
 static int launch_bwd(const AttnArgs& p, int rows, hipStream_t st) {
     const size_t lds_q = (size_t)2 * NKT * 16 * LDSROW * sizeof(bf16_t) + NKT * 16 * (sizeof(int) + 1);
     const size_t lds_kv = (size_t)2 * NKT * 16 * LDSROW * sizeof(bf16_t) + NKT * 16 * (2 * sizeof(float) + sizeof(int) + 1);
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<NKT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<NKT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_dq_kernel<NKT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_dkv_kernel<NKT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv));
-        attr = true;
-    }
+    const dim3 grid(rows * p.H), block(ATT_THREADS);
     const bool generic = p.mask_mode != MASK_NONE || p.bias || p.kvalid;
     // exact-tile backward: correct for any S <= NKT*16 (padded keys have zero K / V rows, padded queries lse = +inf); used where at most
     // three of the NKT key tiles are padding
-    if constexpr (NKT <= 16) if (!generic && (p.Dws || !g_attn_bwd_two_pass) && p.S > (NKT - 3) * 16) {
+    bool exact = false;
+    if constexpr (NKT <= 16) exact = !generic && (p.Dws || !g_attn_bwd_two_pass) && p.S > (NKT - 3) * 16;
+    // (the branches stand in the order in which their kernels have always been emitted into the code object: tools/isa_digest.py compares whole files)
+    if (generic) {
+        if (const int rc = svla_launch<attn_bwd_dq_kernel<NKT, true>>(grid, block, lds_q, st, p)) return rc;
+        return svla_launch<attn_bwd_dkv_kernel<NKT, true>>(grid, block, lds_kv, st, p);
+    }
+    if (!exact) {
+        if (const int rc = svla_launch<attn_bwd_dq_kernel<NKT, false>>(grid, block, lds_q, st, p)) return rc;
+        return svla_launch<attn_bwd_dkv_kernel<NKT, false>>(grid, block, lds_kv, st, p);
+    }
+    if constexpr (NKT <= 16) {
         const size_t le_q = (size_t)2 * NKT * 16 * LDSROW * sizeof(bf16_t);
         const size_t le_kv = le_q + NKT * 16 * 2 * sizeof(float);
-        static bool attr_e = false;
-        if (!attr_e) {
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_dq_exact_kernel<NKT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)le_q));
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_dkv_exact_kernel<NKT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)le_kv));
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_fused_exact_kernel<NKT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)le_kv));
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_bwd_fused_exact_kernel<NKT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)le_kv));
-            attr_e = true;
-        }
         if (g_attn_bwd_two_pass) {
-            hipLaunchKernelGGL((attn_bwd_dq_exact_kernel<NKT>), dim3(rows * p.H), dim3(ATT_THREADS), le_q, st, p);
-            hipLaunchKernelGGL((attn_bwd_dkv_exact_kernel<NKT>), dim3(rows * p.H), dim3(ATT_THREADS), le_kv, st, p);
-        } else {
-#ifdef ATT_TIMING
-            AttnArgs pt = p; if (getenv("SVLA_ATTN_DBGBUF")) pt.kvalid = (const unsigned char*)strtoull(getenv("SVLA_ATTN_DBGBUF"), nullptr, 16);
-            if (p.drop.thr) { hipLaunchKernelGGL((attn_bwd_fused_exact_kernel<NKT, true>), dim3(rows * p.H), dim3(ATT_THREADS), le_kv, st, pt); return svla_launch_status(); }
-#endif
-            if (p.drop.thr) hipLaunchKernelGGL((attn_bwd_fused_exact_kernel<NKT, true>), dim3(rows * p.H), dim3(ATT_THREADS), le_kv, st, p);
-            else hipLaunchKernelGGL((attn_bwd_fused_exact_kernel<NKT, false>), dim3(rows * p.H), dim3(ATT_THREADS), le_kv, st, p);
+            if (const int rc = svla_launch<attn_bwd_dq_exact_kernel<NKT>>(grid, block, le_q, st, p)) return rc;
+            return svla_launch<attn_bwd_dkv_exact_kernel<NKT>>(grid, block, le_kv, st, p);
         }
-        return svla_launch_status();
+#ifdef ATT_TIMING
+        AttnArgs pt = p; if (getenv("SVLA_ATTN_DBGBUF")) pt.kvalid = (const unsigned char*)strtoull(getenv("SVLA_ATTN_DBGBUF"), nullptr, 16);
+        if (p.drop.thr) return svla_launch<attn_bwd_fused_exact_kernel<NKT, true>>(grid, block, le_kv, st, pt);
+#endif
+        if (p.drop.thr) return svla_launch<attn_bwd_fused_exact_kernel<NKT, true>>(grid, block, le_kv, st, p);
+        return svla_launch<attn_bwd_fused_exact_kernel<NKT, false>>(grid, block, le_kv, st, p);
     }
-    if (generic) {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<NKT, true>), dim3(rows * p.H), dim3(ATT_THREADS), lds_q, st, p);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<NKT, true>), dim3(rows * p.H), dim3(ATT_THREADS), lds_kv, st, p);
-    } else {
-        hipLaunchKernelGGL((attn_bwd_dq_kernel<NKT, false>), dim3(rows * p.H), dim3(ATT_THREADS), lds_q, st, p);
-        hipLaunchKernelGGL((attn_bwd_dkv_kernel<NKT, false>), dim3(rows * p.H), dim3(ATT_THREADS), lds_kv, st, p);
-    }
-    return svla_launch_status();
+    return SVLA_EINVAL;      // not reached: NKT > 16 has no exact kernels
 }
 
 // ------------------------------------------------------------------------------------------------ single-query ("decode") forward
@@ -1309,8 +1291,7 @@ extern "C" int svla_attn_fwd_bf16(const bf16_t* Q, const bf16_t* K, const bf16_t
     p.xcd_rows = 0;      // (measured on the persistent forward: +1.5 % time with whole rows per XCD -- its next-item prefetch already hides the fetch; -1.4 % on the backward)
     hipStream_t st = (hipStream_t)stream;
     if (p.Sq == 1 && !bias && mask_mode == MASK_NONE && !p.drop.thr && !g_attn_no_decode) {      // one query per row: read the valid keys only (KV-cached acting step)
-        SVLA_LAUNCH(attn_decode_kernel, attn_decode_kernel_body, DEC_THREADS, 1, dim3(rows * H), dim3(DEC_THREADS), 0, st, p);
-        return svla_launch_status();
+        return SVLA_LAUNCH(attn_decode_kernel, attn_decode_kernel_body, DEC_THREADS, 1, dim3(rows * H), dim3(DEC_THREADS), 0, st, p);
     }
     if (S <= 64) return launch_fwd<4>(p, rows, st);
     if (S <= 128) return launch_fwd<8>(p, rows, st);

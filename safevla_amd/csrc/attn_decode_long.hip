@@ -158,6 +158,5 @@ int attn_decode_long_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, l
                             const unsigned char* kvalid, long ldq, int kv_rows, void* stream) {
     if (rows <= 0 || S <= 0 || S > DECL_MAXS || (ld % 8) || (ldq % 8) || H <= 0 || kv_rows < S) return SVLA_EINVAL;
     DecLongArgs p{Q, K, V, ld, O, ldo, LSE, kvalid, S, H, scale, kv_rows, ldq};
-    SVLA_LAUNCH(attn_decode_long_kernel, attn_decode_long_kernel_body, DECL_THREADS, 1, dim3(rows * H), dim3(DECL_THREADS), 0, (hipStream_t)stream, p);
-    return svla_launch_status();
+    return SVLA_LAUNCH(attn_decode_long_kernel, attn_decode_long_kernel_body, DECL_THREADS, 1, dim3(rows * H), dim3(DECL_THREADS), 0, (hipStream_t)stream, p);
 }

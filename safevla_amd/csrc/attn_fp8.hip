@@ -502,29 +502,15 @@ template <int NKT>
 static int f8_launch_fwd(const Fp8Args& p, int rows, hipStream_t st) {
     constexpr int SP = NKT * 16;
     const size_t lds = SP * 64 + 64 * (SP + 16);
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_fp8_fwd_kernel<NKT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_fp8_fwd_kernel<NKT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    if (p.drop.thr) hipLaunchKernelGGL((attn_fp8_fwd_kernel<NKT, true>), dim3(rows * p.H), dim3(F8_THREADS), lds, st, p);
-    else hipLaunchKernelGGL((attn_fp8_fwd_kernel<NKT, false>), dim3(rows * p.H), dim3(F8_THREADS), lds, st, p);
-    return svla_launch_status();
+    if (p.drop.thr) return svla_launch<attn_fp8_fwd_kernel<NKT, true>>(dim3(rows * p.H), dim3(F8_THREADS), lds, st, p);
+    return svla_launch<attn_fp8_fwd_kernel<NKT, false>>(dim3(rows * p.H), dim3(F8_THREADS), lds, st, p);
 }
 template <int NKT>
 static int f8_launch_bwd(const Fp8Args& p, int rows, hipStream_t st) {
     constexpr int SP = NKT * 16;
     const size_t lds = 2 * SP * 64 + 2 * 64 * (SP + 16) + 2 * SP * sizeof(float);
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_fp8_bwd_kernel<NKT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_fp8_bwd_kernel<NKT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    if (p.drop.thr) hipLaunchKernelGGL((attn_fp8_bwd_kernel<NKT, true>), dim3(rows * p.H), dim3(F8_THREADS), lds, st, p);
-    else hipLaunchKernelGGL((attn_fp8_bwd_kernel<NKT, false>), dim3(rows * p.H), dim3(F8_THREADS), lds, st, p);
-    return svla_launch_status();
+    if (p.drop.thr) return svla_launch<attn_fp8_bwd_kernel<NKT, true>>(dim3(rows * p.H), dim3(F8_THREADS), lds, st, p);
+    return svla_launch<attn_fp8_bwd_kernel<NKT, false>>(dim3(rows * p.H), dim3(F8_THREADS), lds, st, p);
 }
 
 extern "C" int svla_attn_fp8_fwd(const unsigned char* ws, const float* scales, bf16_t* O, long ldo, float* LSE, int rows, int S, int H,

@@ -483,37 +483,19 @@ template <int NKT> constexpr size_t a96_lds_dkv() { return a96_lds_kv<NKT>() + N
 template <int NKT>
 static int a96_launch_fwd(const Attn96Args& p, int rows, hipStream_t st) {
     constexpr size_t lds = a96_lds_kv<NKT>();
-    static bool attr = false;
-    if (!attr) {      // more than the 64 KiB a kernel gets without asking
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn96_fwd_kernel<NKT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn96_fwd_kernel<NKT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
     const dim3 grid(rows * p.H > 0 ? rows * p.H : 1);      // one workgroup per (row, head); rows, H >= 1 is checked by the caller
-    if (p.mask_mode != MASK_NONE || p.kvalid) hipLaunchKernelGGL((attn96_fwd_kernel<NKT, true>), grid, dim3(A96_THREADS), lds, st, p);
-    else hipLaunchKernelGGL((attn96_fwd_kernel<NKT, false>), grid, dim3(A96_THREADS), lds, st, p);
-    return svla_launch_status();
+    if (p.mask_mode != MASK_NONE || p.kvalid) return svla_launch<attn96_fwd_kernel<NKT, true>>(grid, dim3(A96_THREADS), lds, st, p);
+    return svla_launch<attn96_fwd_kernel<NKT, false>>(grid, dim3(A96_THREADS), lds, st, p);
 }
 template <int NKT>
 static int a96_launch_bwd(const Attn96Args& p, int rows, hipStream_t st) {
     constexpr size_t lds_q = a96_lds_kv<NKT>(), lds_kv = a96_lds_dkv<NKT>();
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn96_bwd_dq_kernel<NKT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn96_bwd_dq_kernel<NKT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_q));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn96_bwd_dkv_kernel<NKT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn96_bwd_dkv_kernel<NKT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_kv));
-        attr = true;
-    }
-    const dim3 grid(rows * p.H > 0 ? rows * p.H : 1);
-    if (p.mask_mode != MASK_NONE || p.kvalid) {
-        hipLaunchKernelGGL((attn96_bwd_dq_kernel<NKT, true>), grid, dim3(A96_THREADS), lds_q, st, p);
-        hipLaunchKernelGGL((attn96_bwd_dkv_kernel<NKT, true>), grid, dim3(A96_THREADS), lds_kv, st, p);
-    } else {
-        hipLaunchKernelGGL((attn96_bwd_dq_kernel<NKT, false>), grid, dim3(A96_THREADS), lds_q, st, p);
-        hipLaunchKernelGGL((attn96_bwd_dkv_kernel<NKT, false>), grid, dim3(A96_THREADS), lds_kv, st, p);
-    }
-    return svla_launch_status();
+    const dim3 grid(rows * p.H > 0 ? rows * p.H : 1), block(A96_THREADS);
+    const bool generic = p.mask_mode != MASK_NONE || p.kvalid;
+    if (const int rc = generic ? svla_launch<attn96_bwd_dq_kernel<NKT, true>>(grid, block, lds_q, st, p)
+                               : svla_launch<attn96_bwd_dq_kernel<NKT, false>>(grid, block, lds_q, st, p)) return rc;
+    return generic ? svla_launch<attn96_bwd_dkv_kernel<NKT, true>>(grid, block, lds_kv, st, p)
+                   : svla_launch<attn96_bwd_dkv_kernel<NKT, false>>(grid, block, lds_kv, st, p);
 }
 
 int attn96_fwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long ld, bf16_t* O, long ldo, float* LSE, int rows, int S, int H,

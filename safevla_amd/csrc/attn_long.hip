@@ -300,22 +300,12 @@ int attn_long_bwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long
     p.Q = Q; p.K = K; p.V = V; p.ld = ld; p.O = O; p.ldo = ldo; p.LSE = LSE; p.dO = dO; p.lddo = lddo;
     p.dQ = dQ; p.dK = dK; p.dV = dV; p.ldd = ldd; p.traj = traj; p.kvalid = kvalid;
     p.S = S; p.H = H; p.mask_mode = mask_mode; p.scale = scale; p.drop = drop_cfg(drop);
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_long_bwd_dq_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)al_lds_dq(512)));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_long_bwd_dq_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)al_lds_dq(512)));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_long_bwd_dkv_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)al_lds_dkv(512)));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)attn_long_bwd_dkv_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)al_lds_dkv(512)));
-        attr = true;
-    }
-    const int SP = (S + 31) & ~31;
+    const int SP = (S + 31) & ~31;      // the LDS image grows with S: the opt-in follows the largest window seen
     hipStream_t st = (hipStream_t)stream;
-    if (mask_mode != MASK_NONE || kvalid) {
-        hipLaunchKernelGGL((attn_long_bwd_dq_kernel<true>), dim3(rows * H), dim3(AL_THREADS), al_lds_dq(SP), st, p);
-        hipLaunchKernelGGL((attn_long_bwd_dkv_kernel<true>), dim3(rows * H), dim3(AL_THREADS), al_lds_dkv(SP), st, p);
-    } else {
-        hipLaunchKernelGGL((attn_long_bwd_dq_kernel<false>), dim3(rows * H), dim3(AL_THREADS), al_lds_dq(SP), st, p);
-        hipLaunchKernelGGL((attn_long_bwd_dkv_kernel<false>), dim3(rows * H), dim3(AL_THREADS), al_lds_dkv(SP), st, p);
-    }
-    return svla_launch_status();
+    const dim3 grid(rows * H), block(AL_THREADS);
+    const bool generic = mask_mode != MASK_NONE || kvalid;
+    if (const int rc = generic ? svla_launch<attn_long_bwd_dq_kernel<true>>(grid, block, al_lds_dq(SP), st, p)
+                               : svla_launch<attn_long_bwd_dq_kernel<false>>(grid, block, al_lds_dq(SP), st, p)) return rc;
+    return generic ? svla_launch<attn_long_bwd_dkv_kernel<true>>(grid, block, al_lds_dkv(SP), st, p)
+                   : svla_launch<attn_long_bwd_dkv_kernel<false>>(grid, block, al_lds_dkv(SP), st, p);
 }

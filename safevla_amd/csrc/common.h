@@ -64,8 +64,6 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, f32x4 c) {
         if (_e != hipSuccess) return (int)_e;      \
     } while (0)
 
-static inline int svla_launch_status() { return (int)hipGetLastError(); }
-
 // ---- counter-based dropout (definition in include/svla.h: svla_dropout) ----------------------------------------------------
 struct svla_dropout { unsigned seed, stream; float p; int row_mult; const unsigned* seed_dev; };
 struct DropCfg { unsigned key, thr; float scale; int row_mult; const unsigned* seed_dev; unsigned stream_key; };   // thr == 0: off

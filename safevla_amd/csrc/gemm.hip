@@ -917,27 +917,15 @@ __global__ void __launch_bounds__(NT256_THREADS, 2) gemm_nt8p_bf16_kernel(GemmNt
 template <int ACT, int AUX, bool DROP>
 static int launch_nt8p_inst(const GemmNtArgs& p, int grid, hipStream_t stream) {
     const size_t lds = (size_t)P8_RING_BYTES + 32768;   // 160 KiB: ring + bias table (N <= 8192)
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_nt8p_bf16_kernel<ACT, AUX, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
     // tower-groupable flavours: plain / ReLU x bias / residual (the fusion encoder's and the compressor's forwards at an acting step)
-    if constexpr (ACT <= 1 && AUX <= 1) SVLA_LAUNCH((gemm_nt8p_bf16_kernel<ACT, AUX, DROP>), (gemm_nt8p_bf16_kernel_body<ACT, AUX, DROP>), NT256_THREADS, 2, dim3(grid), dim3(NT256_THREADS), lds, stream, p);
-    else hipLaunchKernelGGL((gemm_nt8p_bf16_kernel<ACT, AUX, DROP>), dim3(grid), dim3(NT256_THREADS), lds, stream, p);
-    return svla_launch_status();
+    if constexpr (ACT <= 1 && AUX <= 1) return SVLA_LAUNCH((gemm_nt8p_bf16_kernel<ACT, AUX, DROP>), (gemm_nt8p_bf16_kernel_body<ACT, AUX, DROP>), NT256_THREADS, 2, dim3(grid), dim3(NT256_THREADS), lds, stream, p);
+    else return svla_launch<gemm_nt8p_bf16_kernel<ACT, AUX, DROP>>(dim3(grid), dim3(NT256_THREADS), lds, stream, p);
 }
 
 template <int ACT, int AUX, bool DROP>
 static int launch_nt256_inst(const GemmNtArgs& p, int grid, hipStream_t stream) {
     const size_t lds = (size_t)NS64 * 512 * BK64 * 2 + 32768;   // 160 KiB
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_nt256k64_bf16_kernel<ACT, AUX, DROP>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr = true;
-    }
-    hipLaunchKernelGGL((gemm_nt256k64_bf16_kernel<ACT, AUX, DROP>), dim3(grid), dim3(NT256_THREADS), lds, stream, p);
-    return svla_launch_status();
+    return svla_launch<gemm_nt256k64_bf16_kernel<ACT, AUX, DROP>>(dim3(grid), dim3(NT256_THREADS), lds, stream, p);
 }
 // Kernel choice (measured, tools/ab_gemm.py, profiles/r03_nt_ab.txt): with the trimmed epilogue the 8-phase kernel wins on every shape of the
 // update (+2 ... +7 %); the 2-buffer kernel stays for N > 8192 (the LDS bias table) and as the A/B partner.  dbg bits 128 / 256 force the
@@ -1009,9 +997,8 @@ static GemmGlobals g_gg;
 static std::once_flag g_gg_once;
 static int gemm_globals_init() {
     std::call_once(g_gg_once, [] {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e == hipSuccess) e = hipDeviceGetAttribute(&g_gg.n_cu, hipDeviceAttributeMultiprocessorCount, dev);
+        g_gg.n_cu = svla_cu_count();
+        hipError_t e = g_gg.n_cu ? hipSuccess : hipErrorInvalidDevice;
         if (e == hipSuccess) e = hipMalloc(&g_gg.zero_bias, 4096 * sizeof(float));
         if (e == hipSuccess) e = hipMemset(g_gg.zero_bias, 0, 4096 * sizeof(float));
         g_gg.rc = (e == hipSuccess) ? svla_asm_preload() : (int)e;      // the assembly code object too: nothing is left to load inside a stream capture
@@ -1035,6 +1022,26 @@ extern "C" int svla_gemm_force_small_tile(int on) {
     if (on >= 10) { g_dbg = on - 10; g_force_small_tile = 0; }
     else { g_dbg = 0; g_force_small_tile = on; }
     return SVLA_OK;
+}
+
+// the 128-tile kernel: one workgroup per 128 x 128 output tile, 66 KiB of LDS = max(NST operand stages 64 KiB, fp32 epilogue tile)
+static int launch_nt128(const GemmNtArgs& p, hipStream_t stream) {
+    const int mt = (p.M + BM - 1) / BM, nt = p.N / BN;
+    const size_t lds = BM * (BN + 4) * sizeof(float);
+    return SVLA_LAUNCH(gemm_nt_bf16_kernel, gemm_nt_bf16_kernel_body, NTHREADS, 2, dim3(mt * nt), dim3(NTHREADS), lds, stream, p);
+}
+// rows [rows_done, M) of p, behind an assembly launch that covered whole 256-row panels: a sub-problem on the 128-tile kernel; row0 keeps its dropout
+// counters and sign-bit blocks on the global row index
+static int nt_tail(const GemmNtArgs& p, size_t rows_done, hipStream_t stream) {
+    GemmNtArgs q = p;
+    q.A = p.A + rows_done * p.lda;
+    q.C = (void*)((bf16_t*)p.C + rows_done * p.ldc);
+    if (p.residual) q.residual = p.residual + rows_done * p.ldr;
+    if (p.bits_in) q.bits_in = p.bits_in + (rows_done >> 5) * (size_t)(p.N >> 6) * 256;
+    if (p.bits_out) q.bits_out = p.bits_out + (rows_done >> 5) * (size_t)(p.N >> 6) * 256;
+    q.M = p.M - (int)rows_done;
+    q.row0 = (int)rows_done;
+    return launch_nt128(q, stream);
 }
 
 // ---- A-stationary assembly kernels (asmgen/nt_as_gen.py): K = 512, bf16 output, full 256-row panels; the M % 256 tail rows run as a
@@ -1136,28 +1143,7 @@ static int nt_as_try(const GemmNtArgs& p, hipStream_t stream) {
     gemm_log(name, npanels * 256, p.N, p.K, (p.bits_in || p.bits_out) ? p.N / 8 : 0);
     const int rc = svla_asm_launch2(name, &k, sizeof(k), k.grid, grid_y, 256, stream);
     if (rc) return rc;
-    const int tail = p.M - npanels * 256;
-    if (tail > 0) {
-        GemmNtArgs q = p;
-        const size_t r0 = (size_t)npanels * 256;
-        q.A = p.A + r0 * p.lda;
-        q.C = (void*)((bf16_t*)p.C + r0 * p.ldc);
-        if (p.residual) q.residual = p.residual + r0 * p.ldr;
-        if (p.bits_in) q.bits_in = p.bits_in + (r0 >> 5) * (size_t)(p.N >> 6) * 256;
-        if (p.bits_out) q.bits_out = p.bits_out + (r0 >> 5) * (size_t)(p.N >> 6) * 256;
-        q.M = tail;
-        q.row0 = (int)r0;
-        const int mt = (tail + BM - 1) / BM, nt = p.N / BN;
-        const size_t lds = BM * (BN + 4) * sizeof(float);
-        static bool attr_set = false;
-        if (!attr_set) {
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_nt_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set = true;
-        }
-        SVLA_LAUNCH(gemm_nt_bf16_kernel, gemm_nt_bf16_kernel_body, NTHREADS, 2, dim3(mt * nt), dim3(NTHREADS), lds, stream, q);
-        return svla_launch_status();
-    }
-    return SVLA_OK;
+    return p.M > npanels * 256 ? nt_tail(p, (size_t)npanels * 256, stream) : SVLA_OK;
 }
 
 // ---- output-stationary assembly kernels (asmgen/nt_os_gen.py): K > 512 (or K = 512 with a residual), bias / residual epilogues without dropout, N % 256 == 0,
@@ -1192,26 +1178,7 @@ static int nt_os_try(const GemmNtArgs& p, hipStream_t stream) {
     gemm_log(name, k.M, p.N, p.K, p.residual ? 2 * p.N : 0);
     const int rc = svla_asm_launch(name, &k, sizeof(k), k.grid, 256, stream);
     if (rc) return rc;
-    const int tail = p.M - mtiles * 256;
-    if (tail > 0) {
-        GemmNtArgs q = p;
-        const size_t r0 = (size_t)mtiles * 256;
-        q.A = p.A + r0 * p.lda;
-        q.C = (void*)((bf16_t*)p.C + r0 * p.ldc);
-        if (p.residual) q.residual = p.residual + r0 * p.ldr;
-        q.M = tail;
-        q.row0 = (int)r0;
-        const int mt = (tail + BM - 1) / BM, nt = p.N / BN;
-        const size_t lds = BM * (BN + 4) * sizeof(float);
-        static bool attr_set = false;
-        if (!attr_set) {
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_nt_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            attr_set = true;
-        }
-        SVLA_LAUNCH(gemm_nt_bf16_kernel, gemm_nt_bf16_kernel_body, NTHREADS, 2, dim3(mt * nt), dim3(NTHREADS), lds, stream, q);
-        return svla_launch_status();
-    }
-    return SVLA_OK;
+    return p.M > mtiles * 256 ? nt_tail(p, (size_t)mtiles * 256, stream) : SVLA_OK;
 }
 
 // fewest 256x256 tiles for which the 256-tile kernel is chosen over the 128-tile one (SVLA_NT256_MIN_TILES: sweep of tools/acting_force_probe.py)
@@ -1241,14 +1208,10 @@ extern "C" int svla_gemm_nt_bf16(const bf16_t* A, long lda, const bf16_t* B, lon
     // N % 256 == 128 with N >= 384 (the ViT-S widths 384 and 1152): the last n-tile is a half tile (75 % / 90 % of the MFMA work useful) --
     // still well ahead of the 128-tile kernel
     if (!out_f32 && ((N % 256) == 0 || ((N % 128) == 0 && N >= 384)) && (K % BK64) == 0 && K >= 2 * BK64 && ((long)((M + 255) / 256) * ((N + 255) / 256) >= nt256_min_tiles() || g_force_small_tile == 2) && g_force_small_tile != 1) {
-        static int n_cu = 0;
-        if (!n_cu) {
-            int dev = 0;
-            HIP_CHECK_RET(hipGetDevice(&dev));
-            HIP_CHECK_RET(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
-            n_cu = (n_cu / 8) * 8;
-            if (n_cu < 8) n_cu = 8;
-        }
+        int n_cu = svla_cu_count();
+        if (!n_cu) return (int)hipErrorInvalidDevice;
+        n_cu = (n_cu / 8) * 8;
+        if (n_cu < 8) n_cu = 8;
         const int ntiles = ((M + 255) / 256) * ((N + 255) / 256);
         gemm_log(nt_use_8p(p) ? "gemm_nt8p_bf16_kernel" : "gemm_nt256k64_bf16_kernel", M, N, K, (p.residual ? 2 * N : 0) + ((p.bits_in || p.bits_out) ? N / 8 : 0) + (p.relu_mask ? 2 * N : 0));
         int grid = n_cu;                       // persistent: one 512-thread workgroup (160 KiB LDS) per CU
@@ -1256,15 +1219,7 @@ extern "C" int svla_gemm_nt_bf16(const bf16_t* A, long lda, const bf16_t* B, lon
         return launch_nt256(p, grid, (hipStream_t)stream);
     }
     gemm_log("gemm_nt_bf16_kernel", M, N, K, 0, false);
-    const int mt = (M + BM - 1) / BM, nt = N / BN;
-    const size_t lds = BM * (BN + 4) * sizeof(float);  // 66 KiB: max(NST operand stages 64 KiB, fp32 epilogue tile)
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_nt_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    SVLA_LAUNCH(gemm_nt_bf16_kernel, gemm_nt_bf16_kernel_body, NTHREADS, 2, dim3(mt * nt), dim3(NTHREADS), lds, (hipStream_t)stream, p);
-    return svla_launch_status();
+    return launch_nt128(p, (hipStream_t)stream);
 }
 
 // RMSNorm(A) . W^T for small M (the frozen T5 encoder's and the llama decoder's pre-norm linears in an acting step: M = 64 ... 768 rows, where the norm was a
@@ -1276,15 +1231,7 @@ extern "C" int svla_gemm_nt_rmsa_bf16(const bf16_t* A, long lda, const bf16_t* B
     if ((lda % 8) || (ldb % 8) || (ldc % 8) || (residual && (ldr % 8))) return SVLA_EINVAL;
     GemmNtArgs p{A, lda, B, ldb, bias, residual, ldr, nullptr, 0, C, ldc, M, N, K, act, 0, 1.f, nullptr, nullptr, drop_cfg(drop), 0, 0, eps};
     gemm_log("gemm_nt_bf16_kernel", M, N, K, 0, false);
-    const int mt = (M + BM - 1) / BM, nt = N / BN;
-    const size_t lds = BM * (BN + 4) * sizeof(float);
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_nt_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    SVLA_LAUNCH(gemm_nt_bf16_kernel, gemm_nt_bf16_kernel_body, NTHREADS, 2, dim3(mt * nt), dim3(NTHREADS), lds, (hipStream_t)stream, p);
-    return svla_launch_status();
+    return launch_nt128(p, (hipStream_t)stream);
 }
 
 // =================================================================================================
@@ -1700,21 +1647,17 @@ __global__ void __launch_bounds__(NT256_THREADS, 2) gemm_tn8p_bf16_kernel(GemmTn
     }
 }
 
-extern "C" int svla_gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* dW, long ldw, float* db, int M,
-                                   int N, int K, void* stream) {
-    if (M <= 0 || (N % 128) || (K % 128) || (ldy % 8) || (ldx % 8)) return SVLA_EINVAL;
-    if (g_force_small_tile == 2 && (N % 256) == 0 && (K % 256) == 0 && M >= 2 * TN256_ROWS && (M % TN256_ROWS) != 0) {
+// force = 0 / 1 / 2: as svla_gemm_force_small_tile
+static int gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* dW, long ldw, float* db, int M, int N, int K, int force, void* stream) {
+    if (force == 2 && (N % 256) == 0 && (K % 256) == 0 && M >= 2 * TN256_ROWS && (M % TN256_ROWS) != 0) {
         // forced big-tile mode (tests: the reference goldens through the kernels that carry the update): whole 64-row groups on the 256-tile
         // kernel, the ragged tail on the small one
         const int mb = M / TN256_ROWS * TN256_ROWS;
-        int rc = svla_gemm_tn_f32acc(dY, ldy, X, ldx, dW, ldw, db, mb, N, K, stream);
+        const int rc = gemm_tn_f32acc(dY, ldy, X, ldx, dW, ldw, db, mb, N, K, 2, stream);
         if (rc) return rc;
-        g_force_small_tile = 1;
-        rc = svla_gemm_tn_f32acc(dY + (size_t)mb * ldy, ldy, X + (size_t)mb * ldx, ldx, dW, ldw, db, M - mb, N, K, stream);
-        g_force_small_tile = 2;
-        return rc;
+        return gemm_tn_f32acc(dY + (size_t)mb * ldy, ldy, X + (size_t)mb * ldx, ldx, dW, ldw, db, M - mb, N, K, 1, stream);
     }
-    if ((N % 256) == 0 && (K % 256) == 0 && (M % TN256_ROWS) == 0 && (M >= 16384 || (M >= 8192 && (long)N * K >= 1024L * 512) || g_force_small_tile == 2) && g_force_small_tile != 1) {
+    if ((N % 256) == 0 && (K % 256) == 0 && (M % TN256_ROWS) == 0 && (M >= 16384 || (M >= 8192 && (long)N * K >= 1024L * 512) || force == 2) && force != 1) {
         // measured (r03): at 16 k rows the 256-tile kernel is 1.0x (512 x 512) to 2.0x (1536 x 512) the 128-tile one, at 8 k rows 0.7x / 1.2-1.9x
         const int ntile256 = (N / 256) * (K / 256);
         int chunks = 256 / ntile256;                                  // <= one workgroup per CU (no second dispatch wave)
@@ -1723,11 +1666,6 @@ extern "C" int svla_gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, 
         chunks = (M + chunk_rows - 1) / chunk_rows;
         GemmTn256Args q{dY, ldy, X, ldx, dW, ldw, db, M, N, K, chunk_rows, g_dbg, g_svla_det};
         const size_t lds256 = (size_t)TN_NS * 2 * TN256_ROWS * 256 * sizeof(bf16_t);   // 128 KiB
-        static bool attr256 = false;
-        if (!attr256) {
-            HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_tn256_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds256));
-            attr256 = true;
-        }
         if (!(g_dbg & (128 | 8192)) && !g_svla_det.i64[0] && !g_svla_det.i64[1] && svla_asm_has("svla_tn_os")) {
             // output-stationary assembly kernel (asmgen/tn_os_gen.py): 4 waves x 128 x 128 accumulators, 4-slot LDS-DMA ring
             struct { const void* dY; long ldy; const void* X; long ldx; float* dW; long ldw; float* db; int M, N, K, chunk_rows, ntile, ntk, grid, pad; } k =
@@ -1737,17 +1675,10 @@ extern "C" int svla_gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, 
             return svla_asm_launch("svla_tn_os", &k, sizeof(k), ntile256 * chunks, 256, (hipStream_t)stream);
         }
         if (!(g_dbg & 128)) {
-            static bool attr8p = false;
-            if (!attr8p) {
-                HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_tn8p_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds256));
-                attr8p = true;
-            }
             gemm_log("gemm_tn8p_bf16_kernel", M, N, K);
-            hipLaunchKernelGGL(gemm_tn8p_bf16_kernel, dim3(ntile256 * chunks), dim3(NT256_THREADS), lds256, (hipStream_t)stream, q);
-            return svla_launch_status();
+            return svla_launch<gemm_tn8p_bf16_kernel>(dim3(ntile256 * chunks), dim3(NT256_THREADS), lds256, (hipStream_t)stream, q);
         }
-        hipLaunchKernelGGL(gemm_tn256_bf16_kernel, dim3(ntile256 * chunks), dim3(NT256_THREADS), lds256, (hipStream_t)stream, q);
-        return svla_launch_status();
+        return svla_launch<gemm_tn256_bf16_kernel>(dim3(ntile256 * chunks), dim3(NT256_THREADS), lds256, (hipStream_t)stream, q);
     }
     if (db) {   // small-tile path: bias gradient as a separate column-sum pass
         const int rc = svla_colsum_bf16(dY, ldy, M, N, 1, db, stream);
@@ -1761,13 +1692,12 @@ extern "C" int svla_gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, 
     chunks = (M + chunk_rows - 1) / chunk_rows;
     GemmTnArgs p{dY, ldy, X, ldx, dW, ldw, M, N, K, chunk_rows, g_svla_det};
     const size_t lds = 2 * 2 * TK * 128 * sizeof(bf16_t);  // 64 KiB
-    static bool attr_set = false;
-    if (!attr_set) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)gemm_tn_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(gemm_tn_bf16_kernel, dim3(ntile * chunks), dim3(NTHREADS), lds, (hipStream_t)stream, p);
-    return svla_launch_status();
+    return svla_launch<gemm_tn_bf16_kernel>(dim3(ntile * chunks), dim3(NTHREADS), lds, (hipStream_t)stream, p);
+}
+extern "C" int svla_gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* dW, long ldw, float* db, int M,
+                                   int N, int K, void* stream) {
+    if (M <= 0 || (N % 128) || (K % 128) || (ldy % 8) || (ldx % 8)) return SVLA_EINVAL;
+    return gemm_tn_f32acc(dY, ldy, X, ldx, dW, ldw, db, M, N, K, g_force_small_tile, stream);
 }
 
 // Column sums (bias gradients): db[n] += sum_m dY[m, n].  HBM-bound single pass, 16-byte loads.

@@ -13,10 +13,12 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <string.h>
+#include <atomic>
+#include <mutex>
 #include <utility>
 
 #define SVLA_MAXG 3             // towers
-#define SVLA_MAXQ 8             // launches one C-ABI call may issue
+#define SVLA_MAXQ 8             // launches one member may defer in one capture (svla_group_begin ... svla_group_end)
 #define SVLA_DEFER_ARG_BYTES 512
 
 template <typename... Ts> struct ArgPack;
@@ -61,6 +63,31 @@ struct GroupCapture {
 };
 GroupCapture* svla_group_capture();    // misc.hip: this thread's open capture, or nullptr
 int svla_group_size();                 // members of the open capture (1: none) -- dispatchers size persistent grids / choose kernels for the GROUP's work
+int svla_cu_count();                   // misc.hip: compute units of the current device, cached (0: the query failed); never refuses inside a stream capture
+
+static inline int svla_launch_status() { return (int)hipGetLastError(); }
+
+// Dynamic LDS beyond 64 KiB has to be asked for, per kernel: raises Kern's limit when `bytes` exceeds what this process has already cleared for it (a high-water
+// mark that starts at 0: sizes below the default limit are asked for too, once, rather than trusting where exactly that default lies).  THE one place that
+// does it -- every launch path below calls it, so no launch site carries a flag of its own -- and so the one place to change if the state ever has to be kept
+// per device (today: once per kernel per process).  Returns the HIP error.
+inline std::mutex& svla_lds_optin_mutex() { static std::mutex m; return m; }
+template <auto Kern> inline int svla_lds_optin(size_t bytes) {
+    static std::atomic<unsigned> cleared{0};
+    if (bytes <= cleared.load(std::memory_order_acquire)) return 0;
+    std::lock_guard<std::mutex> lock(svla_lds_optin_mutex());      // first launches only: two threads must not set the limit in one order and record it in the other
+    if (bytes <= cleared.load(std::memory_order_relaxed)) return 0;
+    const hipError_t e = hipFuncSetAttribute((const void*)Kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return (int)e;
+    cleared.store((unsigned)bytes, std::memory_order_release);
+    return 0;
+}
+// A kernel without a grouped twin: opt in when needed, launch, report.  (Kern may be a template-id with commas: this is a function template, not a macro.)
+template <auto Kern, typename... As> inline int svla_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const As&... a) {
+    if (const int rc = svla_lds_optin<Kern>(lds)) return rc;
+    hipLaunchKernelGGL(Kern, grid, block, lds, s, a...);
+    return svla_launch_status();
+}
 
 // issue n >= 1 members' argument blocks as ONE grid of the grouped twin (grid.z = n)
 template <auto Body, int MAXT, int MINB, typename... Ts>
@@ -68,12 +95,7 @@ inline int svla_twin_launch(const DeferredLaunch* const* m, int n, hipStream_t s
     using Pack = ArgPack<Ts...>;
     GroupedArgs<Pack> g;
     for (int i = 0; i < SVLA_MAXG; ++i) memcpy((void*)&g.a[i], m[i < n ? i : 0]->args, sizeof(Pack));
-    static unsigned attr_smem = 0;      // dynamic LDS this twin has been cleared for (the single-launch kernels set theirs at their launch sites)
-    if (m[0]->smem > attr_smem) {
-        const hipError_t e = hipFuncSetAttribute((const void*)svla_grouped<Body, MAXT, MINB, Ts...>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)m[0]->smem);
-        if (e != hipSuccess) return (int)e;
-        attr_smem = m[0]->smem;
-    }
+    if (const int rc = svla_lds_optin<svla_grouped<Body, MAXT, MINB, Ts...>>(m[0]->smem)) return rc;      // the twin is a kernel of its own: cleared apart from the single-launch kernel
     dim3 grid = m[0]->grid;
     grid.z = (unsigned)n;
     hipLaunchKernelGGL((svla_grouped<Body, MAXT, MINB, Ts...>), grid, m[0]->block, m[0]->smem, s, g);
@@ -94,27 +116,25 @@ template <typename... Ts, void (*Kern)(Ts...), void (*Body)(Ts...), int MAXT, in
 struct Launch<Kern, Body, MAXT, MINB> {
     using Pack = ArgPack<Ts...>;
     template <size_t... I>
-    static void single(const DeferredLaunch& d, hipStream_t s, std::index_sequence<I...>) {
+    static int single(const DeferredLaunch& d, hipStream_t s, std::index_sequence<I...>) {
         Pack p;
         memcpy((void*)&p, d.args, sizeof(Pack));
-        hipLaunchKernelGGL(Kern, d.grid, d.block, d.smem, s, pack_get<I>(p)...);
+        return svla_launch<Kern>(d.grid, d.block, d.smem, s, pack_get<I>(p)...);
     }
     static int flush(const DeferredLaunch* const* m, int n, hipStream_t s) {
-        if (n == 1) {
-            single(*m[0], s, std::index_sequence_for<Ts...>{});
-            return (int)hipGetLastError();
-        }
+        if (n == 1) return single(*m[0], s, std::index_sequence_for<Ts...>{});
         return svla_twin_launch<Body, MAXT, MINB, Ts...>(m, n, s);
     }
-    static void go(dim3 grid, dim3 block, size_t smem, hipStream_t s, Ts... a) {
+    // 0 when the launch was deferred, else its status
+    static int go(dim3 grid, dim3 block, size_t smem, hipStream_t s, Ts... a) {
         GroupCapture* gc = svla_group_capture();
-        if (!gc || gc->n[gc->member] >= SVLA_MAXQ) {      // (no call issues SVLA_MAXQ launches; if one ever does, it is launched at once and the capture is marked)
+        if (!gc || gc->n[gc->member] >= SVLA_MAXQ) {      // (no member defers SVLA_MAXQ launches in a capture; if one ever does, the launch is issued at once and the capture is marked)
             if (gc) gc->overflow = 1;
-            hipLaunchKernelGGL(Kern, grid, block, smem, s, a...);
-            return;
+            return svla_launch<Kern>(grid, block, smem, s, a...);
         }
         svla_defer_fill<Ts...>(gc->q[gc->member][gc->n[gc->member]], &flush, grid, block, smem, s, a...);
         gc->n[gc->member] += 1;
+        return 0;
     }
 };
 // A kernel that exists ONLY as the grouped form: a single launch is a group of one (grid.z = 1).  For the attention forward kernels: their bodies inlined into a

@@ -53,8 +53,7 @@ __global__ void fusion_fill_kernel(const float* __restrict__ fusion_token, const
 extern "C" int svla_fusion_fill(const float* fusion_token, const bf16_t* text, const int* gid, int R, int S, int L,
                                 int text_off, int D, bf16_t* x0, void* stream) {
     if (R <= 0 || text_off + L > S || D <= 0 || (D % 8)) return SVLA_EINVAL;
-    SVLA_LAUNCH(fusion_fill_kernel, fusion_fill_kernel_body, 1024, 1, dim3(R), dim3(64), 0, (hipStream_t)stream, fusion_token, text, gid, R, S, L, text_off, D, x0);
-    return svla_launch_status();
+    return SVLA_LAUNCH(fusion_fill_kernel, fusion_fill_kernel_body, 1024, 1, dim3(R), dim3(64), 0, (hipStream_t)stream, fusion_token, text, gid, R, S, L, text_off, D, x0);
 }
 
 // dtext[gid[r], j, :] += dx0[r, text_off + j, :].  Rows are (t*B + b); an env's goal is constant over an episode,
@@ -134,9 +133,8 @@ extern "C" int svla_decoder_embed_fwd(const bf16_t* xf, long xf_row_stride, cons
                                       const int64_t* hand, const int64_t* time_step, int T, int B, int n_actions, int D, bf16_t* out,
                                       void* stream) {
     if (T <= 0 || B <= 0 || D <= 0 || (D % 8)) return SVLA_EINVAL;
-    SVLA_LAUNCH(decoder_embed_kernel, decoder_embed_kernel_body, 1024, 1, dim3((T * B + 3) / 4), dim3(256), 0, (hipStream_t)stream, xf, xf_row_stride, act_tab,
+    return SVLA_LAUNCH(decoder_embed_kernel, decoder_embed_kernel_body, 1024, 1, dim3((T * B + 3) / 4), dim3(256), 0, (hipStream_t)stream, xf, xf_row_stride, act_tab,
                        hand_tab, div_term, prev_actions, masks, hand, time_step, T, B, n_actions, D, out);
-    return svla_launch_status();
 }
 
 // dxf[(t*B+b) row, :] = dout[b*T+t, :];  d act_tab / d hand_tab accumulated in LDS per block, then flushed.
@@ -200,19 +198,11 @@ extern "C" int svla_decoder_embed_bwd(const bf16_t* dout, const int64_t* prev_ac
     if (lds > 160 * 1024) return SVLA_EINVAL;
     int blocks = (T * B + 63) / 64;
     if (blocks > 128) blocks = 128;
-    static bool attr = false;
-    if (!attr) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)decoder_embed_bwd_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)decoder_embed_bwd_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr = true;
-    }
-    if (det)
-        hipLaunchKernelGGL(decoder_embed_bwd_kernel<true>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, dout, prev_actions, masks, hand,
-                           T, B, n_actions, D, dxf, dxf_row_stride, d_act_tab, d_hand_tab, g_svla_det);
-    else
-        hipLaunchKernelGGL(decoder_embed_bwd_kernel<false>, dim3(blocks), dim3(256), lds, (hipStream_t)stream, dout, prev_actions, masks, hand,
-                           T, B, n_actions, D, dxf, dxf_row_stride, d_act_tab, d_hand_tab, g_svla_det);
-    return svla_launch_status();
+    if (!det)
+        return svla_launch<decoder_embed_bwd_kernel<false>>(dim3(blocks), dim3(256), lds, (hipStream_t)stream, dout, prev_actions, masks, hand,
+                                                            T, B, n_actions, D, dxf, dxf_row_stride, d_act_tab, d_hand_tab, g_svla_det);
+    return svla_launch<decoder_embed_bwd_kernel<true>>(dim3(blocks), dim3(256), lds, (hipStream_t)stream, dout, prev_actions, masks, hand,
+                                                       T, B, n_actions, D, dxf, dxf_row_stride, d_act_tab, d_hand_tab, g_svla_det);
 }
 
 // ---- deterministic accumulation: configuration and fold-back (common.h: DetCfg) -------------------------------------------------
@@ -309,8 +299,7 @@ __global__ void swiglu_bwd_kernel(const bf16_t* __restrict__ ab, const bf16_t* _
 extern "C" int svla_swiglu_fwd(const bf16_t* ab, long M, int Hd, bf16_t* g, void* stream) {
     if (M <= 0 || (Hd % 8)) return SVLA_EINVAL;
     long blocks = (M * (Hd / 8) + 255) / 256; if (blocks > 2048) blocks = 2048;
-    SVLA_LAUNCH(swiglu_fwd_kernel, swiglu_fwd_kernel_body, 1024, 1, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ab, M, Hd, g);
-    return svla_launch_status();
+    return SVLA_LAUNCH(swiglu_fwd_kernel, swiglu_fwd_kernel_body, 1024, 1, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ab, M, Hd, g);
 }
 extern "C" int svla_swiglu_bwd(const bf16_t* ab, const bf16_t* dg, long M, int Hd, bf16_t* dab, void* stream) {
     if (M <= 0 || (Hd % 8)) return SVLA_EINVAL;
@@ -455,8 +444,7 @@ __global__ void embed_gather_kernel(const float* __restrict__ table, const int64
                                     bf16_t* __restrict__ out) { embed_gather_kernel_body(table, ids, n, D, out); }
 extern "C" int svla_embed_gather_f32_bf16(const float* table, const int64_t* ids, long n, int D, bf16_t* out, void* stream) {
     if (n <= 0 || (D % 2)) return SVLA_EINVAL;
-    SVLA_LAUNCH(embed_gather_kernel, embed_gather_kernel_body, 1024, 1, dim3((int)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, ids, n, D, out);
-    return svla_launch_status();
+    return SVLA_LAUNCH(embed_gather_kernel, embed_gather_kernel_body, 1024, 1, dim3((int)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, table, ids, n, D, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -693,8 +681,7 @@ extern "C" int svla_dropout_bf16(bf16_t* x, long rows, int N, const svla_dropout
     if (!c.thr) return SVLA_OK;
     const long n8 = rows * N / 8;
     long blocks = (n8 + 255) / 256; if (blocks > 4096) blocks = 4096;
-    SVLA_LAUNCH(dropout_rows_kernel, dropout_rows_kernel_body, 1024, 1, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, n8, N, c);
-    return svla_launch_status();
+    return SVLA_LAUNCH(dropout_rows_kernel, dropout_rows_kernel_body, 1024, 1, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, n8, N, c);
 }
 
 
@@ -716,8 +703,7 @@ extern "C" int svla_kv_append_bf16(const bf16_t* src, long ld_src, bf16_t* cache
                                    void* stream) {
     if (B <= 0 || width <= 0 || (width % 8) || (ld_src % 8) || !t_dev) return SVLA_EINVAL;
     int blocks = (B * (width / 8) + 255) / 256; if (blocks > 1024) blocks = 1024;
-    SVLA_LAUNCH(kv_append_kernel, kv_append_kernel_body, 1024, 1, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, ld_src, cache, cache_rows, width, t_dev, B);
-    return svla_launch_status();
+    return SVLA_LAUNCH(kv_append_kernel, kv_append_kernel_body, 1024, 1, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src, ld_src, cache, cache_rows, width, t_dev, B);
 }
 
 // ---- inputs of a recorded acting step -> the static buffers the recorded launches read (include/svla.h: svla_acting_stage) --------------------------
@@ -776,6 +762,13 @@ static thread_local GroupCapture* t_group_open = nullptr;      // this thread's 
 static thread_local GroupCapture* t_group_store = nullptr;     // allocated once per thread (~13 KiB of argument blocks)
 GroupCapture* svla_group_capture() { return t_group_open; }
 int svla_group_size() { return t_group_open ? t_group_open->size : 1; }
+// compute units of the current device, asked once per process (a failed query is not remembered).  A plain attribute query: legal inside a stream capture
+int svla_cu_count() {
+    static std::atomic<int> n_cu{0};
+    int n = n_cu.load(std::memory_order_relaxed), dev = 0;
+    if (!n && hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) n_cu.store(n, std::memory_order_relaxed);
+    return n;
+}
 extern "C" int svla_group_begin(int members) {
     if (t_group_open || members < 1 || members > SVLA_MAXG) return SVLA_EINVAL;
     if (!t_group_store) t_group_store = new GroupCapture();

@@ -220,15 +220,14 @@ static int norm_fwd_launch(const T* x, int xG, int xGS, int xOFF, const float* g
     if (tok && tok_group <= 0) return SVLA_EINVAL;
     RowMap xm{xG, xGS, xOFF}, ym{yG, yGS, yOFF};
     dim3 grid(norm_grid(rows, 2048)), block(256);
-#define NORM_FWD_CASE(DD) SVLA_LAUNCH((norm_fwd_kernel<T, DD>), (norm_fwd_kernel_body<T, DD>), 1024, 1, grid, block, 0, (hipStream_t)stream, x, xm, gamma, beta, eps, rows, rms, relu, tok, tok_group, y, ym, mean, rstd)
+#define NORM_FWD_CASE(DD) return SVLA_LAUNCH((norm_fwd_kernel<T, DD>), (norm_fwd_kernel_body<T, DD>), 1024, 1, grid, block, 0, (hipStream_t)stream, x, xm, gamma, beta, eps, rows, rms, relu, tok, tok_group, y, ym, mean, rstd)
     // widths on this path: 512 (policy, T5), 384 / 768 / 1024 (frozen ViT-S / ViT-B + SigLIP-B / ViT-L preprocessors)
     if (D == 512) NORM_FWD_CASE(512);
     else if (D == 384) NORM_FWD_CASE(384);
     else if (D == 768) NORM_FWD_CASE(768);
     else if (D == 1024) NORM_FWD_CASE(1024);
-    else return SVLA_EINVAL;
+    return SVLA_EINVAL;
 #undef NORM_FWD_CASE
-    return svla_launch_status();
 }
 
 template <typename T>

@@ -414,9 +414,8 @@ extern "C" int svla_small_linear_fwd_f32(const float* x, const float* W, const f
                                          int B, float* out, void* stream) {
     if (D <= 0 || D > 1024 || (D % 8) || N <= 0 || N > 32 || rows <= 0) return SVLA_EINVAL;
     if (T > 0 && T * B != rows) return SVLA_EINVAL;
-    SVLA_LAUNCH(small_linear_fwd_kernel<32>, small_linear_fwd_kernel_body<32>, 1024, 1, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, W, bias,
+    return SVLA_LAUNCH(small_linear_fwd_kernel<32>, small_linear_fwd_kernel_body<32>, 1024, 1, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, x, W, bias,
                        rows, N, D, T, B, out);
-    return svla_launch_status();
 }
 
 extern "C" int svla_small_linear_bwd_f32(const float* x, const float* W, const float* dout, int rows, int N, int D, int T,
