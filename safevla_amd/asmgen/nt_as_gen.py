@@ -36,7 +36,8 @@ whole (carry chains through SCC, M0 write + DMA).
 import os as _os
 
 from . import gelu_poly
-from .amdasm import EXEC, M0, Prog, a, s, v
+from .amdasm import EXEC, M0, a, s, v
+from .kernelgen import Kernarg, KernelGen
 
 KS_DEFAULT = 32            # k-steps of 16 (K = 512); the ViT-S flavours run K = 384 (24 k-steps: 192 of the 256 AGPRs hold A)
 LDS_W = (0, 65536)
@@ -47,9 +48,10 @@ LDS_BYTES = 163840
 # ---- kernel arguments (byte offsets in the kernarg segment)
 # nr: columns of the n-range one workgroup sweeps (= N for the row-streaming launches; N / nsplit for the mid-M launches whose grid is (panel slots,
 # nsplit): workgroup_id_y picks the range [y * nr, (y + 1) * nr)); flags bit 0: no phases (every wave of a workgroup starts its sweep in step 0)
-KARG = dict(A=0, lda=8, B=16, ldb=24, bias=32, res=40, nr=48, flags=52, C=56, ldc=64, cmask=72, N=76, alpha=80, npanels=84, bits=88,
-            key=96, thr=100, scale=104, row_mult=108, seed_dev=112, stream_key=120, grid=124)
-KARG_BYTES = 128
+KARG = Kernarg("NtAsKarg", [("A", "ptr"), ("lda", "i64"), ("B", "ptr"), ("ldb", "i64"), ("bias", "ptr"), ("res", "ptr"), ("nr", "i32"), ("flags", "i32"), ("C", "ptr"),
+                            ("ldc", "i64"), ("cmask", "i32"), ("N", "i32"), ("alpha", "f32"), ("npanels", "i32"), ("bits", "ptr"), ("key", "u32"), ("thr", "u32"),
+                            ("scale", "f32"), ("row_mult", "i32"), ("seed_dev", "ptr"), ("stream_key", "u32"), ("grid", "i32")])
+KARG_BYTES = KARG.nbytes      # (the name the block size had before Kernarg: kept for callers that size their own buffer)
 
 # ---- SGPRs (s0..s3 are free after the prologue: timing builds use them)
 S_A, S_LDA, S_B, S_LDB, S_BIAS, S_RES, S_LDR, S_C = s(4, 2), s(6, 2), s(8, 2), s(10, 2), s(12, 2), s(14, 2), s(16, 2), s(18, 2)
@@ -128,35 +130,15 @@ def XFRAG(mb, ks, KS=KS_DEFAULT):
     return a((mb * KS + ks) * 4, 4)
 
 
-class QModel:
-    """In-order completion queue (VM or LGKM) as the generator sees it: tags of the operations issued and not yet known retired."""
-
-    def __init__(self, maxcnt):
-        self.q = []
-        self.maxcnt = maxcnt
-
-    def issue(self, tag):
-        self.q.append(tag)
-
-    def need(self, tags):
-        """largest count n such that waiting for 'at most n outstanding' retires every tag in tags; None if none of them is in the queue"""
-        idx = [i for i, t in enumerate(self.q) if t in tags]
-        if not idx:
-            return None
-        return min(len(self.q) - 1 - max(idx), self.maxcnt)
-
-    def wait(self, n):
-        self.q = self.q[len(self.q) - n:] if n > 0 else []
-
-
-class NtAsGen:
+class NtAsGen(KernelGen):
+    KARG, LDS_BYTES, N_SGPR = KARG, LDS_BYTES, N_SGPR
     CAP = 3            # filler groups per MFMA gap taken from the streams (fixed-slot instructions come on top)
     PF_GAP = 24        # bits_in: the sign-bit words of this step's slabs are requested here (consumed ~100 gaps later)
     DMA_END = 72       # the last LDS-DMA piece of the next tile is issued by this gap (~1.5 k cycles before the barrier)
     BAR_GAP = 119      # the barrier follows MFMA 119 (k-step 29); the last fragment reads of the tile are issued at gaps 113 / 115
 
-    def __init__(self, name="svla_nt_as_f0", relu=False, drop=False, bits_out=False, bits_in=False, cap=None, dbg="", stagger=0, epi_order=1, dma_end=None, store_nt=True, load_nt=False, xstart=0, wphases=4, xburst=2, K=512, gelu=False):
-        self.name = name
+    def __init__(self, name="svla_nt_as_f0", relu=False, drop=False, bits_out=False, bits_in=False, dbg="", wphases=4, xburst=2, K=512, gelu=False):
+        super().__init__(name, dbg)      # dbg: time, nostore, nodma, nox, noepi, nobarwait, nobias
         self.gelu = gelu          # epilogue = erf-GELU(acc + bias) as the polynomial of asmgen/gelu_poly.py (the frozen ViT's fc1)
         assert not (gelu and (relu or drop or bits_out or bits_in))
         assert K in (384, 512)
@@ -169,56 +151,11 @@ class NtAsGen:
         self.relu, self.drop, self.bits_out, self.bits_in = relu, drop, bits_out, bits_in
         self.bias = not bits_in
         assert not (bits_in and (relu or drop or bits_out)) and (not bits_out or relu) and (not drop or relu)
-        self.dbg = set(dbg.split(",")) if dbg else set()      # timing-only / bisection builds (tools/): time, nostore, nodma, nox, noepi, ...
-        if cap is not None:
-            self.CAP = cap
-        self.stagger, self.epi_order, self.store_nt, self.load_nt, self.xstart = stagger, epi_order, store_nt, load_nt, xstart
-        # panel switch: the 4 fragment loads (k-steps 4j .. 4j+3 of one row block) that share a 128-byte line of A are issued back to back (2; 1: row blocks
-        # interleaved, 3: two lines per burst, 4: row blocks half a period apart, 0: each load as soon as its register is free).  Measured (profiles/
-        # r04_nt_as_step_timing.txt): 2 = 4 > 3 > 0 > 1 -- a fragment-shaped load touches 32 bytes of 32 lines, and the L1 does not keep a line for the 600 cycles
-        # until the next k-step's load comes for its next 32 bytes
+        # panel switch: the fragment loads (k-steps 4j .. 4j+3 of one row block) that share a 128-byte line of A are issued back to back (2: what ships;
+        # 3: two lines per burst; 0: each load as soon as its register is free).  Ranking of the bursts tried: DESIGN_HISTORY.md
+        assert xburst in (0, 2, 3)
         self.xburst = xburst
         self.wphases = wphases      # 4: every wave of a workgroup switches panels in its own step; 2: in pairs; 1: all in the same step
-        if dma_end is not None:
-            self.DMA_END = dma_end
-        self.p = Prog(name)
-        self.vm = QModel(63)
-        self.lg = QModel(15)
-        self.uid = 0
-        self.stats = {}
-
-    # ------------------------------------------------------------------ helpers
-    def tag(self, base):
-        self.uid += 1
-        return f"{base}#{self.uid}"
-
-    def wait_for(self, vm_tags=(), lg_tags=()):
-        nv = self.vm.need(set(vm_tags)) if vm_tags else None
-        nl = self.lg.need(set(lg_tags)) if lg_tags else None
-        if nv is None and nl is None:
-            return
-        self.p.s_waitcnt(vmcnt=nv, lgkmcnt=nl)
-        if nv is not None:
-            self.vm.wait(nv)
-        if nl is not None:
-            self.lg.wait(nl)
-
-    def lg_room(self):
-        # the LGKM counter has 4 bits: never let the model's queue pass 15 (LDS operations retire in order within ~100 cycles, so in
-        # steady state this wait finds its operations long retired)
-        if len(self.lg.q) >= 15:
-            self.p.s_waitcnt(lgkmcnt=11)
-            self.lg.wait(11)
-
-    def ds_read(self, d, addr, off, tag):
-        self.lg_room()
-        self.p.ds_read(d, addr, off)
-        self.lg.issue(tag)
-
-    def ds_write(self, addr, src, off=0):
-        self.lg_room()
-        self.p.ds_write(addr, src, off)
-        self.lg.issue(self.tag("dsw"))
 
     # ------------------------------------------------------------------ prologue
     def prologue(self):
@@ -401,9 +338,7 @@ class NtAsGen:
                 for th in grp:
                     th()
         p.s_xor_b32(S_M0NEXT, S_M0NEXT, 0x10000)
-        p.s_waitcnt(vmcnt=0, lgkmcnt=0)
-        self.vm.wait(0)
-        self.lg.wait(0)
+        self.wait_all()
         if self.bias:
             self.bias_table()
             p.s_waitcnt(lgkmcnt=0)
@@ -542,12 +477,12 @@ class NtAsGen:
         nv = self.vm.need({f"dma{t}" for t in range(16)})
         if "time" in self.dbg:
             p.s_memtime(s(0, 2))
-        if "nobarwait" in self.dbg:      # timing-only: no wait for the DMA at the barrier (wrong results)
-            p.s_waitcnt(lgkmcnt=0)
+        nv = nv if nv is not None else 0
+        if "nobarwait" in self.dbg:      # timing-only: no wait for the DMA at the barrier (wrong results; the model goes on as if it had waited)
+            self.wait_all(vm=None)
+            self.vm.wait(nv)
         else:
-            p.s_waitcnt(vmcnt=nv if nv is not None else 0, lgkmcnt=0)
-        self.vm.wait(nv if nv is not None else 0)
-        self.lg.wait(0)
+            self.wait_all(vm=nv)
         if "time" in self.dbg and kind != "dummy":
             ki = {"first": 0, "mid": 1, "last": 2}[kind]
             p.s_sub_u32(s(3), s(0), s(28))
@@ -556,17 +491,6 @@ class NtAsGen:
         if "time" in self.dbg:
             p.s_mov_b32(s(28), s(0))
         p.s_barrier()
-        if self.stagger and kind != "dummy":
-            # the four waves leave the barrier in the same cycle and run the same stream: every LDS read / DMA issue of the step would
-            # collide with the other three waves' (measured: SQ_WAIT_INST_LDS = 1.5 quad-cycles per MFMA).  Wave w idles w * (stagger + ~3)
-            # issue slots here, so the waves sit at different offsets inside the 32-cycle MFMA period until the next barrier.
-            self.uid += 1
-            done = f"L_STG{self.uid}"
-            for i in range(1, 4):
-                p.s_cmp("lt_u32", S_WID, i)
-                p.s_cbranch_scc1(done)
-                p.s_nop(self.stagger - 1)
-            p.label(done)
 
     def step_tail_scalars(self):
         p = self.p
@@ -576,7 +500,7 @@ class NtAsGen:
 
     # ------------------------------------------------------------------ epilogue of one n-step (previous step's accumulators)
     def epi_stream(self, st, masked, earliest, late=None):
-        """list of (earliest_gap, [thunks]): the epilogue of accumulator set st, stores optionally under S_STMASK.  Order (epi_order 1):
+        """list of (earliest_gap, [thunks]): the epilogue of accumulator set st, stores optionally under S_STMASK.  Order:
         convert + stage slab 0, read it back, convert + stage slab 1 (LDS operations of a wave execute in order: the writes follow the
         reads), store slab 0, read slab 1 back, [late: groups of the caller, e.g. the next step's bias reads], store slab 1 -- no store waits
         for a read-back issued just ahead of it."""
@@ -724,14 +648,14 @@ class NtAsGen:
                     else:
                         p.s_mov_b64(EXEC, S_LO32)
                     p.buffer_store(v(OBW[0].idx, 2), V_C8, SRD_B, S_T[2 + mb])
-                    self.vm.issue(self.tag("stb"))
+                    self.vm.issue(self.uniq("stb#"))
                     p.s_mov_b64(EXEC, -1)
                 add(bits_store)
 
         def readback(mb):
             tags = []
             for it in range(4):
-                tg = self.tag(f"rb{mb}_{it}")
+                tg = self.uniq(f"rb{mb}_{it}#")
                 tags.append(tg)
                 def rb(it=it, tg=tg, mb=mb):
                     if it & 1:
@@ -751,24 +675,18 @@ class NtAsGen:
                         return
                     if masked:
                         p.s_mov_b64(EXEC, S_STMASK)
-                    p.buffer_store(V_RB[mb][it], V_CSTEP, SRD_C, S_CROW[mb * 4 + it], nt=self.store_nt)
-                    self.vm.issue(self.tag("st"))
+                    p.buffer_store(V_RB[mb][it], V_CSTEP, SRD_C, S_CROW[mb * 4 + it], nt=True)
+                    self.vm.issue(self.uniq("st#"))
                     if masked:
                         p.s_mov_b64(EXEC, -1)
                 add(st_)
-        if self.epi_order == 0:
-            for mb in range(2):
-                convert(mb)
-                stores(mb, readback(mb))
-            items += late or []
-        else:
-            convert(0)
-            t0 = readback(0)
-            convert(1)
-            stores(0, t0)
-            t1 = readback(1)
-            items += late or []
-            stores(1, t1)
+        convert(0)
+        t0 = readback(0)
+        convert(1)
+        stores(0, t0)
+        t1 = readback(1)
+        items += late or []
+        stores(1, t1)
         return items
 
     # ------------------------------------------------------------------ one n-step body
@@ -826,40 +744,23 @@ class NtAsGen:
             p.s_sub_u32(S_T[7], S_NPANELS, 1)
             p.s_min_u32(S_PN, S_PN, S_T[7])
             self.panel_srd(SRD_X, S_A, S_PN, S_LDA2)
-            for ks in range(KS):
-                for mb in range(2):
-                    def xl(ks=ks, mb=mb):
-                        if "nox" in self.dbg:
-                            return
-                        p.buffer_load(XFRAG(mb, ks, self.KS), V_XOFF[mb], SRD_X, S_XROW, ks * 32, nt=self.load_nt)
-                        self.vm.issue(f"x{ks}")
-                    if self.xburst:
-                        continue
-                    fixed[max(4 * ks + 3, self.xstart + (2 * ks + mb) // 2 if self.xstart else 0)].append(xl)
-            if self.xburst:
-                def xl2(ks, mb):
-                    def f():
-                        if "nox" in self.dbg:
-                            return
-                        p.buffer_load(XFRAG(mb, ks, self.KS), V_XOFF[mb], SRD_X, S_XROW, ks * 32, nt=self.load_nt)
-                        self.vm.issue(f"x{ks}")
-                    return f
-                if self.xburst == 3:          # two lines (8 k-steps) per burst
-                    for j in range(KS // 8):
-                        for mb in range(2):
-                            for ks in range(8 * j, 8 * j + 8):
-                                fixed[32 * j + 31].append(xl2(ks, mb))
-                elif self.xburst == 4:        # the two row blocks half a line period apart
-                    for j in range(KS // 4):
-                        for mb in range(2):
-                            for ks in range(4 * j, 4 * j + 4):
-                                fixed[min(16 * j + 15 + 8 * mb, 4 * KS - 1)].append(xl2(ks, mb))
-                else:
-                    for j in range(KS // 4):
-                        order = [(ks, mb) for ks in range(4 * j, 4 * j + 4) for mb in range(2)] if self.xburst == 1 else \
-                                [(ks, mb) for mb in range(2) for ks in range(4 * j, 4 * j + 4)]
-                        for ks, mb in order:
-                            fixed[16 * j + 15].append(xl2(ks, mb))
+            def xl(ks, mb):
+                def f():
+                    if "nox" in self.dbg:
+                        return
+                    p.buffer_load(XFRAG(mb, ks, self.KS), V_XOFF[mb], SRD_X, S_XROW, ks * 32)
+                    self.vm.issue(f"x{ks}")
+                return f
+            if self.xburst == 0:
+                for ks in range(KS):
+                    for mb in range(2):
+                        fixed[4 * ks + 3].append(xl(ks, mb))
+            else:
+                per = 4 * (self.xburst - 1)       # k-steps per burst: the 4 of a line, or 8
+                for j in range(KS // per):
+                    for mb in range(2):
+                        for ks in range(per * j, per * j + per):
+                            fixed[4 * per * (j + 1) - 1].append(xl(ks, mb))
         if kind == "first":
             for ks in range(KS):
                 pre[4 * ks].append(("vm", f"x{ks}"))
@@ -870,7 +771,7 @@ class NtAsGen:
             late.append((16, [lambda: p.v_add_u32(V_BIASSTEP, S_NB4, V_BIASRD)]))
             for nb in range(2):
                 for rg in range(4):
-                    late.append((16, [lambda nb=nb, rg=rg: self.ds_read(BIASR(nb).sub(4 * rg, 4), V_BIASSTEP, nb * 128 + rg * 32, self.tag("bias"))]))
+                    late.append((16, [lambda nb=nb, rg=rg: self.ds_read(BIASR(nb).sub(4 * rg, 4), V_BIASSTEP, nb * 128 + rg * 32, self.uniq("bias#"))]))
         epi = self.epi_stream(st ^ 1, masked=(kind == "first"), earliest=8, late=late) if "noepi" not in self.dbg else late
         epi.append((16, [self.step_tail_scalars]))
         if kind == "first":
@@ -888,7 +789,6 @@ class NtAsGen:
         # (the CU's L1 <-> L2 path is the resource this kernel saturates: measured)
         windows = [(1, self.DMA_END), (8, BAR - 1)]
         pos = [0] * len(streams)
-        nfill = 0
         for g in range(NG):
             ks, i = divmod(g, 4)
             nb, mb = divmod(i, 2)
@@ -911,7 +811,6 @@ class NtAsGen:
                             th()
                         pos[si] += 1
                         n += 1
-                        nfill += 1
             if g == BAR - 1:
                 # every DMA piece the barrier's vmcnt must cover and every LDS operation of the epilogue has been issued: the LGKM queue a
                 # step starts with is the six fragment reads behind the barrier, whatever step preceded it
@@ -920,15 +819,12 @@ class NtAsGen:
                         for th in sm[pos[si]][1]:
                             th()
                         pos[si] += 1
-                        nfill += 1
-        self.stats[(kind, st)] = nfill
 
     def dummy_body(self):
         """a step of a wave that has no panel in flight (before its first / after its last): its share of the DMA, the barrier, the
         fragment reads behind it (never consumed: they keep the LGKM state every step starts with), no MFMA, no epilogue"""
         p = self.p
-        p.s_waitcnt(lgkmcnt=0)          # the fragment / bias reads the previous step left in flight: nobody consumes them here
-        self.lg.wait(0)
+        self.wait_all(vm=None)          # the fragment / bias reads the previous step left in flight: nobody consumes them here
         self.step_head()
         for t in range(16):
             for grp in self.dma_groups(t):
@@ -940,7 +836,7 @@ class NtAsGen:
             p.v_add_u32(V_BIASSTEP, S_NB4, V_BIASRD)          # the next step may be this wave's first real one: its accumulator initialiser
             for nb in range(2):
                 for rg in range(4):
-                    self.ds_read(BIASR(nb).sub(4 * rg, 4), V_BIASSTEP, nb * 128 + rg * 32, self.tag("bias"))
+                    self.ds_read(BIASR(nb).sub(4 * rg, 4), V_BIASSTEP, nb * 128 + rg * 32, self.uniq("bias#"))
         self.barrier("dummy")
         for k in range(3):
             for nb in range(2):
@@ -958,9 +854,7 @@ class NtAsGen:
         p.s_sub_u32(S_DUM, S_DUM, 1)
         p.s_branch("L_DUMA")
         # the first generated body (LAST) is entered from a MID step at run time: seed the queue models with what such a step leaves behind
-        real, self.p = self.p, Prog("scratch")
-        self.body("mid", 0)
-        self.p = real
+        self.scratch(lambda: self.body("mid", 0))
         p.label("L_LAST")
         self.body("last", 1)
         p.s_add_u32(S_P, S_P, S_GRID)
@@ -979,9 +873,7 @@ class NtAsGen:
         p.s_branch("L_LAST")
         p.label("L_DRAIN")
         # the last step's epilogue (accumulator set 1), nothing to hide it under; the fragments prefetched for a non-existent next step drain
-        p.s_waitcnt(vmcnt=0, lgkmcnt=0)
-        self.vm.wait(0)
-        self.lg.wait(0)
+        self.wait_all()
         for _, grp in self.epi_stream(1, masked=False, earliest=0):
             for th in grp:
                 th()
@@ -1015,68 +907,6 @@ class NtAsGen:
             p.s_waitcnt(vmcnt=0)
         p.s_endpgm()
         return self
-
-    # ------------------------------------------------------------------ assembly text
-    def asm_text(self):
-        body = self.p.text()
-        name = self.name
-        return f"""// GENERATED by safevla_amd/asmgen/nt_as_gen.py -- do not edit.
-\t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"
-\t.text
-\t.protected {name}
-\t.globl {name}
-\t.p2align 8
-\t.type {name},@function
-{name}:
-{body}
-.L{name}_end:
-\t.size {name}, .L{name}_end-{name}
-
-\t.rodata
-\t.p2align 6
-\t.amdhsa_kernel {name}
-\t\t.amdhsa_group_segment_fixed_size {LDS_BYTES}
-\t\t.amdhsa_private_segment_fixed_size 0
-\t\t.amdhsa_kernarg_size {KARG_BYTES}
-\t\t.amdhsa_user_sgpr_count 2
-\t\t.amdhsa_user_sgpr_kernarg_segment_ptr 1
-\t\t.amdhsa_system_sgpr_workgroup_id_x 1
-\t\t.amdhsa_system_sgpr_workgroup_id_y 1
-\t\t.amdhsa_system_sgpr_workgroup_id_z 0
-\t\t.amdhsa_system_vgpr_workitem_id 0
-\t\t.amdhsa_next_free_vgpr 512
-\t\t.amdhsa_next_free_sgpr {N_SGPR}
-\t\t.amdhsa_accum_offset 256
-\t\t.amdhsa_reserve_vcc 1
-\t\t.amdhsa_float_round_mode_32 0
-\t\t.amdhsa_float_round_mode_16_64 0
-\t\t.amdhsa_float_denorm_mode_32 3
-\t\t.amdhsa_float_denorm_mode_16_64 3
-\t\t.amdhsa_dx10_clamp 1
-\t\t.amdhsa_ieee_mode 1
-\t.end_amdhsa_kernel
-
-\t.amdgpu_metadata
----
-amdhsa.version: [ 1, 2 ]
-amdhsa.target: amdgcn-amd-amdhsa--gfx950
-amdhsa.kernels:
-  - .name: {name}
-    .symbol: {name}.kd
-    .kernarg_segment_size: {KARG_BYTES}
-    .group_segment_fixed_size: {LDS_BYTES}
-    .private_segment_fixed_size: 0
-    .kernarg_segment_align: 8
-    .wavefront_size: 64
-    .sgpr_count: {N_SGPR + 6}
-    .vgpr_count: 512
-    .agpr_count: 256
-    .max_flat_workgroup_size: 256
-    .args:
-      - {{ .size: {KARG_BYTES}, .offset: 0, .value_kind: by_value }}
-...
-\t.end_amdgpu_metadata
-"""
 
 
 # flavour -> generator options (the C dispatcher nt_as_try of csrc/gemm.hip picks by name)

@@ -23,15 +23,18 @@ GEMMs through linear1 (K = 2048) and in_proj (K = 1536), linear2's forward in ev
     stores are DEFERRED into the MFMA gaps of the next tile's first two K-tiles (the operand DMA of the next tile runs on under all of it).
 Every wait is counted by the generator's queue models and checked by amdasm.Emu (tests/test_asm_emulator_cpu.py).
 """
-from .amdasm import M0, Prog, a, s, v
-from .nt_as_gen import QModel
+import os as _os
+
+from .amdasm import M0, a, s, v
+from .kernelgen import Kernarg, KernelGen
 
 LDS_STG = 131072            # + wave * 4096
 LDS_BIAS = 147456           # fp32 bias[N], N <= 4096
 LDS_BYTES = 163840
 PARB, WOFF, UNIT = 65536, 32768, 4096       # ring: [K-tile parity][A units 0..7 | W units 0..7][32 rows][128 B]
-KARG = dict(A=0, lda=8, B=16, ldb=24, bias=32, res=40, ldr=48, C=56, ldc=64, M=72, N=76, K=80, ntn=84, ntiles=88, grid=92)
-KARG_BYTES = 96
+KARG = Kernarg("NtOsKarg", [("A", "ptr"), ("lda", "i64"), ("B", "ptr"), ("ldb", "i64"), ("bias", "ptr"), ("res", "ptr"), ("ldr", "i64"), ("C", "ptr"), ("ldc", "i64"),
+                            ("M", "i32"), ("N", "i32"), ("K", "i32"), ("ntn", "i32"), ("ntiles", "i32"), ("grid", "i32")])
+KARG_BYTES = KARG.nbytes      # (the name the block size had before Kernarg: kept for callers that size their own buffer)
 
 S_A, S_LDA, S_B, S_LDB, S_BIAS, S_RES, S_LDR, S_C = s(4, 2), s(6, 2), s(8, 2), s(10, 2), s(12, 2), s(14, 2), s(16, 2), s(18, 2)
 S_LDC, S_M, S_N, S_K, S_NTN, S_NTILES, S_GRID = s(20, 2), s(22), s(23), s(24), s(25), s(26), s(27)
@@ -86,61 +89,14 @@ V_T = [v(248 + i) for i in range(8)]                   # prologue only
 SRD_P = SRD_T                                          # C descriptor of the PREVIOUS tile (deferred stores); the bias-table descriptor in the prologue
 
 
-class NtOsGen:
+class NtOsGen(KernelGen):
+    KARG, LDS_BYTES, N_SGPR = KARG, LDS_BYTES, N_SGPR
+
     def __init__(self, name="svla_nt_os_p", bias=False, res=False, dbg=""):
-        self.name, self.bias, self.res = name, bias, res
-        self.dbg = set(dbg.split(",")) if dbg else set()
-        self.p = Prog(name)
-        self.vm = QModel(63)
-        self.lg = QModel(15)
-        self.uid = 0
+        super().__init__(name, dbg)
+        self.bias, self.res = bias, res
 
     # ------------------------------------------------------------------ helpers
-    def lab(self, base):
-        self.uid += 1
-        return f"L_{base}{self.uid}"
-
-    def wait_for(self, vm_tags=(), lg_tags=()):
-        nv = self.vm.need(set(vm_tags)) if vm_tags else None
-        nl = self.lg.need(set(lg_tags)) if lg_tags else None
-        if nv is None and nl is None:
-            return
-        self.p.s_waitcnt(vmcnt=nv, lgkmcnt=nl)
-        if nv is not None:
-            self.vm.wait(nv)
-        if nl is not None:
-            self.lg.wait(nl)
-
-    def lg_room(self):
-        if len(self.lg.q) >= 15:
-            self.p.s_waitcnt(lgkmcnt=11)
-            self.lg.wait(11)
-
-    def ds_read(self, d, addr, off, tag):
-        self.lg_room()
-        self.p.ds_read(d, addr, off)
-        self.lg.issue(tag)
-
-    def ds_write(self, addr, src, off=0):
-        self.lg_room()
-        self.p.ds_write(addr, src, off)
-        self.uid += 1
-        self.lg.issue(f"dsw#{self.uid}")
-
-    def divmod(self, q, r, num, den):
-        """q, r = num / den, num % den by repeated subtraction (small quotients; runs once per kernel)"""
-        p = self.p
-        top, done = self.lab("DIV"), self.lab("DIVD")
-        p.s_mov_b32(q, 0)
-        p.s_mov_b32(r, num)
-        p.label(top)
-        p.s_cmp("lt_u32", r, den)
-        p.s_cbranch_scc1(done)
-        p.s_sub_u32(r, r, den)
-        p.s_add_u32(q, q, 1)
-        p.s_branch(top)
-        p.label(done)
-
     def tile_ptrs(self, xdst, wdst, mt, nt):
         """addresses of (row 0, k = 0) of the A row tile mt and of the W row tile nt"""
         p = self.p
@@ -155,7 +111,7 @@ class NtOsGen:
         """K-tile T + 1 <- T + 2; T + 2 <- the K-tile after it (the next 64 k of its output tile, or the first of this workgroup's next tile;
         past the last tile the cursor wraps onto that tile again: fetched, never computed)"""
         p = self.p
-        adv, stay, done = self.lab("ADV"), self.lab("STAY"), self.lab("CUR")
+        adv, stay, done = self.uniq("L_ADV"), self.uniq("L_STAY"), self.uniq("L_CUR")
         for i in range(2):
             p.s_mov_b32(S_X1.sub(i), S_X2.sub(i))
             p.s_mov_b32(S_W1.sub(i), S_W2.sub(i))
@@ -224,25 +180,9 @@ class NtOsGen:
         p.s_lshl_b32(S_M0W, S_WID, 10)
         # ---- workgroup -> first tile: XCD-contiguous virtual index (workgroup b runs on XCD b % 8): the n-tiles of a row tile share an L2
         p.s_mov_b32(S_T[0], s(2))
-        p.s_lshr_b32(S_T[1], S_GRID, 3)             # q = grid / 8
-        p.s_and_b32(S_T[2], S_GRID, 7)              # r = grid % 8
-        p.s_and_b32(S_T[3], S_T[0], 7)              # xcd
-        p.s_lshr_b32(S_T[4], S_T[0], 3)             # slot
-        p.s_add_u32(S_T[5], S_T[1], 1)
-        lo, xd = self.lab("XLO"), self.lab("XD")
-        p.s_cmp("lt_u32", S_T[3], S_T[2])
-        p.s_cbranch_scc1(lo)
-        p.s_mul_i32(S_T[6], S_T[2], S_T[5])
-        p.s_sub_u32(S_T[7], S_T[3], S_T[2])
-        p.s_mul_i32(S_T[7], S_T[7], S_T[1])
-        p.s_add_u32(S_T[6], S_T[6], S_T[7])
-        p.s_branch(xd)
-        p.label(lo)
-        p.s_mul_i32(S_T[6], S_T[3], S_T[5])
-        p.label(xd)
-        p.s_add_u32(S_TC, S_T[6], S_T[4])           # vid
-        self.divmod(S_MTC, S_NTC, S_TC, S_NTN)
-        self.divmod(S_DQ, S_DR, S_GRID, S_NTN)
+        self.xcd_vid(S_TC, S_T, S_GRID, self.uniq("L_XLO"), self.uniq("L_XD"))
+        self.divmod(S_MTC, S_NTC, S_NTN, self.uniq("L_DIV"), self.uniq("L_DIVD"), num=S_TC)
+        self.divmod(S_DQ, S_DR, S_NTN, self.uniq("L_DIV"), self.uniq("L_DIVD"), num=S_GRID)
         p.s_mov_b32(S_TD, S_TC)
         p.s_mov_b32(S_MTD, S_MTC)
         p.s_mov_b32(S_NTD, S_NTC)
@@ -340,17 +280,14 @@ class NtOsGen:
         self.tile_setup()
         p.s_lshr_b32(S_LOOP, S_KT, 1)
         p.s_sub_u32(S_LOOP, S_LOOP, 2)
-        p.s_waitcnt(vmcnt=0, lgkmcnt=0)
-        self.vm.wait(0)
-        self.lg.wait(0)
+        self.wait_all()
         p.s_barrier()
         for ks in range(4):
             self.xread(0, 0, 0, ks)
         for nb in range(4):
             for ks in range(4):
                 self.wread(0, nb, ks)
-        p.s_waitcnt(lgkmcnt=0)
-        self.lg.wait(0)
+        self.wait_all(vm=None)
 
     def bias_table(self):
         p = self.p
@@ -363,7 +300,7 @@ class NtOsGen:
         p.s_mov_b32(S_T[3], 0)
         p.s_lshl_b32(S_T[4], S_N, 2)
         p.s_mov_b32(SRD_T.sub(2), S_T[4])
-        top = self.lab("BIAS")
+        top = self.uniq("L_BIAS")
         p.label(top)
         p.buffer_load(T[2], T[0], SRD_T, S_T[3])
         p.s_waitcnt(vmcnt=0)
@@ -452,8 +389,7 @@ class NtOsGen:
                 p.s_mul_i32(S_T[5], S_LDC2, mb * 32 + 8 * it)
                 if "nostore" not in self.dbg:
                     p.buffer_store(OUTQ(slab, it), V_COFF, SRD_P, S_T[5], j * 128, nt=True)
-                    self.uid += 1
-                    self.vm.issue(f"st#{self.uid}")
+                    self.vm.issue(self.uniq("st#"))
             groups.append(st)
         return groups
 
@@ -518,16 +454,8 @@ class NtOsGen:
         self.cursor_next()
 
     def barrier(self, vm_tags, lg_tags):
-        p = self.p
-        nv = self.vm.need(set(vm_tags))
-        nl = self.lg.need(set(lg_tags))
-        if nv is not None or nl is not None:
-            p.s_waitcnt(vmcnt=nv, lgkmcnt=nl)
-            if nv is not None:
-                self.vm.wait(nv)
-            if nl is not None:
-                self.lg.wait(nl)
-        p.s_barrier()
+        self.wait_for(vm_tags, lg_tags)
+        self.p.s_barrier()
 
     # ------------------------------------------------------------------ exposed half of the epilogue: accumulators -> bf16 pieces
     def pack(self):
@@ -583,13 +511,6 @@ class NtOsGen:
         convert(len(quads) - 1)
 
     # ------------------------------------------------------------------ whole kernel
-    def scratch(self, *bodies):
-        """advance the queue models over a code sequence without emitting it (what precedes a body that is entered from later code at run time)"""
-        real, self.p = self.p, Prog("scratch")
-        for b in bodies:
-            b()
-        self.p = real
-
     def build(self):
         p = self.p
         self.prologue()
@@ -629,8 +550,7 @@ class NtOsGen:
         p.s_branch("L_TILE")
         p.label("L_EXIT")
         # the last tile's deferred half, nothing to hide it under
-        p.s_waitcnt(lgkmcnt=0)
-        self.lg.wait(0)
+        self.wait_all(vm=None)
         if "noepi" not in self.dbg:
             for slab in range(8):
                 for g in self.drain_groups(slab):
@@ -639,22 +559,10 @@ class NtOsGen:
         p.s_endpgm()
         return self
 
-    def asm_text(self):
-        from . import nt_as_gen as G
-        g = G.NtAsGen(name=self.name)
-        g.p = self.p
-        t = g.asm_text()
-        t = t.replace(f".amdhsa_kernarg_size {G.KARG_BYTES}", f".amdhsa_kernarg_size {KARG_BYTES}").replace(
-            f".kernarg_segment_size: {G.KARG_BYTES}", f".kernarg_segment_size: {KARG_BYTES}").replace(
-            f".size: {G.KARG_BYTES}, .offset: 0", f".size: {KARG_BYTES}, .offset: 0")
-        return t.replace("nt_as_gen.py", "nt_os_gen.py")
-
 
 # flavour -> generator options (the C dispatcher nt_os_try of csrc/gemm.hip picks by name)
 FLAVOURS = {"p": dict(), "b": dict(bias=True), "r": dict(res=True), "br": dict(bias=True, res=True)}
 
-
-import os as _os
 if _os.environ.get("SVLA_ASM_DEBUG_VARIANTS"):      # timing-only builds (tools/var_nt_os.py): wrong results
     for _d in ("noepi", "nodma", "nomfma", "nostore", "noepi,nodma", "noepi,nomfma"):
         FLAVOURS["r_" + _d.replace(",", "_")] = dict(res=True, dbg=_d)

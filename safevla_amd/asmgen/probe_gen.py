@@ -1,14 +1,15 @@
 """Hardware probes of the assembly builder's assumptions (tools/asm_probe.py): what the launch puts into s2 / v0, the raw buffer descriptor path,
 the saddr form of global_load_lds, MFMA operands in AGPRs, buffer loads into AGPRs.  Built only with SVLA_ASM_DEBUG_VARIANTS=1."""
-from .amdasm import M0, Prog, a, s, v
-from . import nt_as_gen as G
+from .amdasm import M0, a, s, v
+from .kernelgen import Kernarg, KernelGen
 
 
-class ProbeGen:
-    name = "svla_probe"
+class ProbeGen(KernelGen):
+    KARG = Kernarg("ProbeKarg", [("out", "ptr"), ("src", "ptr"), ("n", "i32"), ("unused0", "i32"), ("unused1", "i64")])      # the s_load below fetches 8 dwords
+    LDS_BYTES, N_SGPR = 163840, 102         # (record 2 uses LDS up to 74112; s64 is the highest register: the values the probe has always shipped with)
 
     def __init__(self):
-        self.p = Prog(self.name)
+        super().__init__("svla_probe")
 
     def build(self):
         p = self.p
@@ -89,9 +90,3 @@ class ProbeGen:
         p.s_waitcnt(vmcnt=0, lgkmcnt=0)
         p.s_endpgm()
         return self
-
-    def asm_text(self):
-        g = G.NtAsGen(name=self.name)
-        g.p = self.p
-        return g.asm_text().replace(f".amdhsa_kernarg_size {G.KARG_BYTES}", ".amdhsa_kernarg_size 32").replace(
-            f".kernarg_segment_size: {G.KARG_BYTES}", ".kernarg_segment_size: 32").replace(f".size: {G.KARG_BYTES}, .offset: 0", ".size: 32, .offset: 0")

@@ -15,13 +15,14 @@ runs over the (huge) row dimension, so the only stationary thing is the OUTPUT:
     (v_dot2c_f32_bf16 against ones), on the waves / workgroups / slots whose turn it is.
 Every wait is counted by the generator's queue models and checked by amdasm.Emu (tests/test_asm_emulator_cpu.py).
 """
-from .amdasm import EXEC, M0, Prog, a, s, v
-from .nt_as_gen import QModel
+from .amdasm import M0, a, s, v
+from .kernelgen import Kernarg, KernelGen
 
 LDS_BYTES = 131072
 SLOT = 32768               # bytes per ring slot: [32 rows][512 B] of dY, then the same of X
-KARG = dict(dY=0, ldy=8, X=16, ldx=24, dW=32, ldw=40, db=48, M=56, N=60, K=64, chunk_rows=68, ntile=72, ntk=76, grid=80)
-KARG_BYTES = 88
+KARG = Kernarg("TnOsKarg", [("dY", "ptr"), ("ldy", "i64"), ("X", "ptr"), ("ldx", "i64"), ("dW", "ptr"), ("ldw", "i64"), ("db", "ptr"), ("M", "i32"), ("N", "i32"),
+                            ("K", "i32"), ("chunk_rows", "i32"), ("ntile", "i32"), ("ntk", "i32"), ("grid", "i32")])
+KARG_BYTES = KARG.nbytes      # (the name the block size had before Kernarg: kept for callers that size their own buffer)
 
 S_DY, S_LDY, S_X, S_LDX, S_DW, S_LDW, S_DB = s(4, 2), s(6, 2), s(8, 2), s(10, 2), s(12, 2), s(14, 2), s(16, 2)
 S_M, S_N, S_K, S_CHUNKROWS, S_NTILE, S_NTK = s(18), s(19), s(20), s(21), s(22), s(23)
@@ -37,7 +38,7 @@ S_M0W = s(58)                                  # w * 4096: this wave's 8 rows in
 S_BTURN, S_DOBIAS = s(59), s(60)
 S_LDW4, S_ROW = s(61), s(62)
 S_T = [s(64 + i) for i in range(12)]
-N_SGPR = 80
+N_SGPR = 102              # (80 would do: s75 is the highest register used.  The value is part of the kernel descriptor the kernel has always shipped with)
 
 
 def ACC(i, j):
@@ -60,25 +61,11 @@ V_ONES, V_OFF, V_LANE = v(88), v(89), v(90)
 V_T = [v(96 + i) for i in range(16)]
 
 
-class TnOsGen:
-    def __init__(self, name="svla_tn_os", dbg=""):
-        self.name = name
-        self.dbg = set(dbg.split(",")) if dbg else set()
-        self.p = Prog(name)
-        self.vm = QModel(63)
-        self.lg = QModel(15)
-        self.uid = 0
+class TnOsGen(KernelGen):
+    KARG, LDS_BYTES, N_SGPR = KARG, LDS_BYTES, N_SGPR
 
-    def wait_for(self, vm_tags=(), lg_tags=()):
-        nv = self.vm.need(set(vm_tags)) if vm_tags else None
-        nl = self.lg.need(set(lg_tags)) if lg_tags else None
-        if nv is None and nl is None:
-            return
-        self.p.s_waitcnt(vmcnt=nv, lgkmcnt=nl)
-        if nv is not None:
-            self.vm.wait(nv)
-        if nl is not None:
-            self.lg.wait(nl)
+    def __init__(self, name="svla_tn_os", dbg=""):
+        super().__init__(name, dbg)
 
     # ------------------------------------------------------------------ prologue
     def prologue(self):
@@ -98,39 +85,10 @@ class TnOsGen:
         p.s_load(S_T[8], s(0, 2), KARG["grid"])
         p.s_mov_b32(S_T[0], s(2))                   # workgroup id
         p.s_waitcnt(lgkmcnt=0)
-        p.s_lshr_b32(S_T[1], S_T[8], 3)             # q = nwg / 8
-        p.s_and_b32(S_T[2], S_T[8], 7)              # r = nwg % 8
-        p.s_and_b32(S_T[3], S_T[0], 7)              # xcd
-        p.s_lshr_b32(S_T[4], S_T[0], 3)             # slot
-        p.s_add_u32(S_T[5], S_T[1], 1)              # q + 1
-        p.s_cmp("lt_u32", S_T[3], S_T[2])
-        p.s_cbranch_scc1("L_XLO")
-        p.s_mul_i32(S_T[6], S_T[2], S_T[5])         # r * (q + 1)
-        p.s_sub_u32(S_T[7], S_T[3], S_T[2])
-        p.s_mul_i32(S_T[7], S_T[7], S_T[1])
-        p.s_add_u32(S_T[6], S_T[6], S_T[7])
-        p.s_branch("L_XD")
-        p.label("L_XLO")
-        p.s_mul_i32(S_T[6], S_T[3], S_T[5])
-        p.label("L_XD")
-        p.s_add_u32(S_T[6], S_T[6], S_T[4])         # vid
-        p.s_mov_b32(S_CHUNK, 0)
-        p.label("L_DIV")
-        p.s_cmp("lt_u32", S_T[6], S_NTILE)
-        p.s_cbranch_scc1("L_DIVD")
-        p.s_sub_u32(S_T[6], S_T[6], S_NTILE)
-        p.s_add_u32(S_CHUNK, S_CHUNK, 1)
-        p.s_branch("L_DIV")
-        p.label("L_DIVD")
+        self.xcd_vid(S_T[6], S_T, S_T[8], "L_XLO", "L_XD")
+        self.divmod(S_CHUNK, S_T[6], S_NTILE, "L_DIV", "L_DIVD")            # vid -> chunk, tile
         p.s_mov_b32(S_TILE, S_T[6])
-        p.s_mov_b32(S_T[7], 0)                      # tile / ntk
-        p.label("L_DIV2")
-        p.s_cmp("lt_u32", S_T[6], S_NTK)
-        p.s_cbranch_scc1("L_DIV2D")
-        p.s_sub_u32(S_T[6], S_T[6], S_NTK)
-        p.s_add_u32(S_T[7], S_T[7], 1)
-        p.s_branch("L_DIV2")
-        p.label("L_DIV2D")
+        self.divmod(S_T[7], S_T[6], S_NTK, "L_DIV2", "L_DIV2D")             # tile -> n-tile, k-tile
         p.s_mov_b32(S_KT, S_T[6])
         p.s_lshl_b32(S_N0, S_T[7], 8)
         p.s_lshl_b32(S_K0, S_T[6], 8)
@@ -265,11 +223,7 @@ class TnOsGen:
         frag = (FA if which == "a" else FB)(f, u)
         off = (pos & 1) * SLOT + st * 8192
         for hi in range(2):
-            if len(self.lg.q) >= 15:
-                self.p.s_waitcnt(lgkmcnt=11)
-                self.lg.wait(11)
-            self.p.ds_read_b64_tr_b16(frag.sub(2 * hi, 2), regs, off + hi * 2048)
-            self.lg.issue(f"f{f}_{which}{u}")
+            self.lg_issue(f"f{f}_{which}{u}", self.p.ds_read_b64_tr_b16, frag.sub(2 * hi, 2), regs, off + hi * 2048)
 
     def kstep(self, x, st, last_of_slot_barrier):
         """16 MFMAs of k-step st of ring position x (register set st), with the next k-step's reads and a share of the DMA in their gaps"""
@@ -288,9 +242,7 @@ class TnOsGen:
             # start of the slot's second k-step: its fragments (the last reads of this slot) have retired -> nobody reads the slot any more;
             # ring position x + 1 has landed (two younger positions = 16 DMA instructions may stay in flight)
             nv = self.vm.need({f"dma{(x + 1) % 4}_{part}_{t}" for part in range(2) for t in range(4)})
-            p.s_waitcnt(vmcnt=nv if nv is not None else 0, lgkmcnt=0)
-            self.vm.wait(nv if nv is not None else 0)
-            self.lg.wait(0)
+            self.wait_all(vm=nv if nv is not None else 0)
             p.s_barrier()
         g = 0
         for i in range(4):
@@ -304,8 +256,7 @@ class TnOsGen:
                     dma.pop(0)()
                 g += 1
         # bias gradient: the dY fragments of this k-step against ones (only where it is this workgroup's / wave's turn)
-        self.uid += 1
-        skip = f"L_NB{self.uid}"
+        skip = self.uniq("L_NB")
         p.s_cmp("eq_u32", S_DOBIAS, 0)
         p.s_cbranch_scc1(skip)
         for u in range(4):
@@ -339,19 +290,13 @@ class TnOsGen:
         p.s_cmp("eq_u32", S_WK, 0)
         p.s_cselect_b32(s(3), s(3), 0)
         # seed the queue models with one scratch pass of the loop body (the loop is entered from itself at run time)
-        real, self.p = self.p, Prog("scratch")
-        lgq, vmq = list(self.lg.q), list(self.vm.q)
-        for x in range(4):
-            self.slot(x)
-        self.p = real
+        self.scratch(*[lambda x=x: self.slot(x) for x in range(4)])
         p.label("L_LOOP")
         for x in range(4):
             self.slot(x)
         p.s_branch("L_LOOP")
         p.label("L_EPI")
-        p.s_waitcnt(vmcnt=0, lgkmcnt=0)
-        self.vm.wait(0)
-        self.lg.wait(0)
+        self.wait_all()
         self.epilogue()
         p.s_endpgm()
         return self
@@ -387,8 +332,7 @@ class TnOsGen:
                 for j in range(4):
                     p.buffer_atomic_add_f32(ACC(i, j).sub(r), V_OFF, SRD_W, S_ROW, 128 * j)
         # bias gradient: lanes c / c + 32 hold the sums over the two row halves of column wn*128 + 32 u + c
-        self.uid += 1
-        done = f"L_BD{self.uid}"
+        done = self.uniq("L_BD")
         p.s_cmp("eq_u32", s(3), 0)
         p.s_cbranch_scc1(done)
         p.s_lshl_b32(S_T[0], S_WN, 7)
@@ -404,18 +348,6 @@ class TnOsGen:
             p.buffer_atomic_add_f32(V_BG[u], T[3], SRD_B, 0, 128 * u)
         p.label(done)
         p.s_waitcnt(vmcnt=0)
-
-    def asm_text(self):
-        from . import nt_as_gen as G
-        g = G.NtAsGen(name=self.name)
-        g.p = self.p
-        t = g.asm_text()
-        t = t.replace(f".amdhsa_kernarg_size {G.KARG_BYTES}", f".amdhsa_kernarg_size {KARG_BYTES}").replace(
-            f".kernarg_segment_size: {G.KARG_BYTES}", f".kernarg_segment_size: {KARG_BYTES}").replace(
-            f".size: {G.KARG_BYTES}, .offset: 0", f".size: {KARG_BYTES}, .offset: 0")
-        t = t.replace(f".amdhsa_group_segment_fixed_size {G.LDS_BYTES}", f".amdhsa_group_segment_fixed_size {LDS_BYTES}").replace(
-            f".group_segment_fixed_size: {G.LDS_BYTES}", f".group_segment_fixed_size: {LDS_BYTES}")
-        return t
 
 
 def generate(dbg=""):

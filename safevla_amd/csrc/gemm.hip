@@ -71,6 +71,7 @@ __device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b) {
 // gelu_poly.py: |error| <= 2.2e-5 for all x, exact tails): 15 plain VALU operations, no transcendental -- round 4's Abramowitz-Stegun form was 17 + v_rcp +
 // v_exp, and the exposed GELU epilogue was 40 % of the ViT's fc1 GEMM.  The assembly GELU flavour (svla_nt_as_k384_f2) evaluates the same polynomial.
 #include "_obj/gelu_poly.h"
+#include "_obj/asm_kargs.h"      // NtAsKarg, NtOsKarg, TnOsKarg: generated from the KARG declarations of asmgen/*_gen.py, layout asserted field by field
 __device__ __forceinline__ float gelu_f(float x) {
     constexpr float c[SVLA_GELU_DEGREE + 1] = SVLA_GELU_COEFS;
     const float t = __builtin_amdgcn_fmed3f(x, -SVLA_GELU_CLAMP, SVLA_GELU_CLAMP);
@@ -1047,11 +1048,6 @@ static int nt_tail(const GemmNtArgs& p, size_t rows_done, hipStream_t stream) {
 // ---- A-stationary assembly kernels (asmgen/nt_as_gen.py): K = 512, bf16 output, full 256-row panels; the M % 256 tail rows run as a
 // sub-problem on the 128-tile kernel (row0 keeps its dropout counters / sign-bit blocks on the global row index).
 #define NT_AS_NOT_TAKEN (-12345)
-struct NtAsKarg {      // = asmgen/nt_as_gen.py KARG
-    const void* A; long lda; const void* B; long ldb; const float* bias; const void* res; int nr, flags; void* C; long ldc;
-    int cmask, N; float alpha; int npanels; const void* bits; unsigned key, thr; float scale; int row_mult; const unsigned* seed_dev; unsigned stream_key; int grid;
-};
-static_assert(sizeof(NtAsKarg) == 128, "kernarg layout of the nt_as kernels");
 // floor of the mid-M launch in 256-row panels (SVLA_NT_AS_MIN_PANELS: sweeps of tools/ab_midm.py; the cost model below decides above it)
 static int nt_as_min_panels() {
     static int v = -1;
@@ -1148,11 +1144,6 @@ static int nt_as_try(const GemmNtArgs& p, hipStream_t stream) {
 
 // ---- output-stationary assembly kernels (asmgen/nt_os_gen.py): K > 512 (or K = 512 with a residual), bias / residual epilogues without dropout, N % 256 == 0,
 // K % 128 == 0, full 256-row tiles; the M % 256 tail rows run on the 128-tile kernel.  g_dbg & 16384 = off (A/B: tools/ab_nt_os.py).
-struct NtOsKarg {      // = asmgen/nt_os_gen.py KARG
-    const void* A; long lda; const void* B; long ldb; const float* bias; const void* res; long ldr; void* C; long ldc;
-    int M, N, K, ntn, ntiles, grid;
-};
-static_assert(sizeof(NtOsKarg) == 96, "kernarg layout of the nt_os kernels");
 static int nt_os_try(const GemmNtArgs& p, hipStream_t stream) {
     if (p.out_f32 || (p.N % 256) || p.N > 4096 || (p.K % 128) || p.K < 384 || (p.dbg & (8192 | 16384)) || g_force_small_tile == 1) return NT_AS_NOT_TAKEN;
     if (p.relu_mask || p.bits_in || p.bits_out || p.drop.thr || p.act != ACT_NONE || p.alpha != 1.f) return NT_AS_NOT_TAKEN;
@@ -1668,9 +1659,7 @@ static int gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, long ldx,
         const size_t lds256 = (size_t)TN_NS * 2 * TN256_ROWS * 256 * sizeof(bf16_t);   // 128 KiB
         if (!(g_dbg & (128 | 8192)) && !g_svla_det.i64[0] && !g_svla_det.i64[1] && svla_asm_has("svla_tn_os")) {
             // output-stationary assembly kernel (asmgen/tn_os_gen.py): 4 waves x 128 x 128 accumulators, 4-slot LDS-DMA ring
-            struct { const void* dY; long ldy; const void* X; long ldx; float* dW; long ldw; float* db; int M, N, K, chunk_rows, ntile, ntk, grid, pad; } k =
-                {dY, ldy, X, ldx, dW, ldw, db, M, N, K, chunk_rows, ntile256, K / 256, ntile256 * chunks, 0};
-            static_assert(sizeof(k) == 88, "kernarg layout of svla_tn_os");
+            TnOsKarg k = {dY, ldy, X, ldx, dW, ldw, db, M, N, K, chunk_rows, ntile256, K / 256, ntile256 * chunks};
             gemm_log("svla_tn_os", M, N, K);
             return svla_asm_launch("svla_tn_os", &k, sizeof(k), ntile256 * chunks, 256, (hipStream_t)stream);
         }

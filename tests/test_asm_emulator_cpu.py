@@ -3,8 +3,6 @@ emulator of asmgen/amdasm.py (asynchronous loads land only at the s_waitcnt that
 against a numpy restatement of the epilogues of csrc/gemm.hip (reference layers: nn.TransformerEncoderLayer linears of
 architecture/models/allenact_transformer_models/allenact_dino_transformer.py:545-552).  CPU only: this is what validates a schedule
 before it is ever run on a GPU; tests/test_kernels_gpu.py compares the same kernels with the HIP kernels on hardware."""
-import struct
-
 import numpy as np
 import pytest
 
@@ -56,17 +54,10 @@ def run_kernel(flavour, M, N, grid, order=None, seed=0, alpha=1.0, key=0x1234567
     q = max(N // 256, 1)
     cmask = 0 if flags & 1 else (1 << (q.bit_length() - 1)) - 1
     for wg, wy in [(x, y) for x in range(min(grid, npanels)) for y in range(nsplit)]:
-        emu = Emu(g.p)
+        emu = Emu(g.p, lds_bytes=g.LDS_BYTES)
         aX, aW, aB, aC, aBits = emu.alloc(X), emu.alloc(W), emu.alloc(bias), emu.alloc(C, writable=True), emu.alloc(bits, writable=True)
-        ka = bytearray(G.KARG_BYTES)
-
-        def put(name, fmt, val):
-            struct.pack_into(fmt, ka, G.KARG[name], val)
-        put("A", "<Q", aX); put("lda", "<q", K); put("B", "<Q", aW); put("ldb", "<q", K); put("bias", "<Q", aB)
-        put("C", "<Q", aC); put("ldc", "<q", N); put("cmask", "<i", cmask); put("N", "<i", N); put("alpha", "<f", alpha)
-        put("npanels", "<i", npanels); put("grid", "<i", grid); put("bits", "<Q", aBits)
-        put("key", "<I", key); put("thr", "<I", thr); put("scale", "<f", float(scale)); put("row_mult", "<i", row_mult)
-        put("nr", "<i", N // nsplit); put("flags", "<i", flags)
+        ka = g.KARG.pack(A=aX, lda=K, B=aW, ldb=K, bias=aB, C=aC, ldc=N, cmask=cmask, N=N, alpha=alpha, npanels=npanels, grid=grid, bits=aBits,
+                         key=key, thr=thr, scale=float(scale), row_mult=row_mult, nr=N // nsplit, flags=flags)
         emu.run(ka, wg, order=order, wg_id_y=wy)
     acc = (bf16_to_f32(X).astype(np.float64) @ bf16_to_f32(W).astype(np.float64).T).astype(np.float32)
     out = bf16_to_f32(C)
@@ -194,15 +185,10 @@ def run_tn(M, N, Kc, chunk_rows, grid, with_bias=True, seed=0):
     dW0, db0 = dW.copy(), db.copy()
     ntk, ntile = Kc // 256, (N // 256) * (Kc // 256)
     for wg in range(grid):
-        emu = Emu(g.p, lds_bytes=T.LDS_BYTES)
+        emu = Emu(g.p, lds_bytes=g.LDS_BYTES)
         aY, aX, aW, aB = emu.alloc(dY), emu.alloc(X), emu.alloc(dW, writable=True), emu.alloc(db, writable=True)
-        ka = bytearray(T.KARG_BYTES)
-
-        def put(name, fmt, val):
-            struct.pack_into(fmt, ka, T.KARG[name], val)
-        put("dY", "<Q", aY); put("ldy", "<q", N); put("X", "<Q", aX); put("ldx", "<q", Kc); put("dW", "<Q", aW); put("ldw", "<q", Kc)
-        put("db", "<Q", aB if with_bias else 0); put("M", "<i", M); put("N", "<i", N); put("K", "<i", Kc); put("chunk_rows", "<i", chunk_rows)
-        put("ntile", "<i", ntile); put("ntk", "<i", ntk); put("grid", "<i", grid)
+        ka = g.KARG.pack(dY=aY, ldy=N, X=aX, ldx=Kc, dW=aW, ldw=Kc, db=aB if with_bias else 0, M=M, N=N, K=Kc, chunk_rows=chunk_rows,
+                         ntile=ntile, ntk=ntk, grid=grid)
         emu.run(ka, wg)
     yf, xf = bf16_to_f32(dY).astype(np.float64), bf16_to_f32(X).astype(np.float64)
     return dW, dW0 + yf.T @ xf, db, db0 + (yf.sum(0) if with_bias else 0)
@@ -234,15 +220,9 @@ def run_nt_os(flavour, M, N, Kc, grid, order=None, seed=0):
     ntn, ntiles = N // 256, (M // 256) * (N // 256)
     grid = min(grid, ntiles)
     for wg in range(grid):
-        emu = Emu(g.p)
+        emu = Emu(g.p, lds_bytes=g.LDS_BYTES)
         aX, aW, aB, aR, aC = emu.alloc(X), emu.alloc(W), emu.alloc(bias), emu.alloc(R), emu.alloc(C, writable=True)
-        ka = bytearray(O.KARG_BYTES)
-
-        def put(name, fmt, val):
-            struct.pack_into(fmt, ka, O.KARG[name], val)
-        put("A", "<Q", aX); put("lda", "<q", Kc); put("B", "<Q", aW); put("ldb", "<q", Kc); put("bias", "<Q", aB); put("res", "<Q", aR); put("ldr", "<q", N)
-        put("C", "<Q", aC); put("ldc", "<q", N); put("M", "<i", M); put("N", "<i", N); put("K", "<i", Kc); put("ntn", "<i", ntn)
-        put("ntiles", "<i", ntiles); put("grid", "<i", grid)
+        ka = g.KARG.pack(A=aX, lda=Kc, B=aW, ldb=Kc, bias=aB, res=aR, ldr=N, C=aC, ldc=N, M=M, N=N, K=Kc, ntn=ntn, ntiles=ntiles, grid=grid)
         emu.run(ka, wg, order=order)
     ref = (bf16_to_f32(X).astype(np.float64) @ bf16_to_f32(W).astype(np.float64).T).astype(np.float32)
     if g.bias:
