@@ -341,6 +341,39 @@ int svla_aug_jitter_blur_u8(const unsigned char* x, unsigned char* y, int B, int
 int svla_aug_resize_post_sharp_u8(const unsigned char* x, unsigned char* y, int B, int H, int W, int top, int left, int bh, int bw, int posterize,
                                   int sharpen, void* stream);
 
+/* ---- per-trajectory random frame augmentation (imitation-learning training from raw frames) ----------------------- */
+/* The IL Preprocessor (architecture/models/transformer_models/preprocessors.py:86-118) applies the FULL random v2 list
+ * (utils/transformation_util.py:12-28; tensor_image_preprocessor with specific=False, preprocessors.py:22-60) once per trajectory and camera, every call with
+ * newly drawn parameters: a batch of B trajectories carries B transforms.  The three entry points below are the three launches above with a table in place
+ * of the by-value transform: image n of x [N,H,W,3] uses entry n / group_len of the [N / group_len] table.  The arithmetic per image is that of the
+ * single-transform launches, bit for bit, with posterize generalised to x & post_mask (the chain RandomPosterize(7), (6), (5), (4) keeps the fewest bits drawn)
+ * and the blur always on (the list applies GaussianBlur unconditionally).
+ *
+ * One table entry, 27 dwords.  nops / ops_packed / f: the call's ColorJitter order as above.  nops_before_contrast: the position of contrast in that order
+ * (the gray partial sums are taken after that many operations), -1 when contrast is not among them.  wx / wy: the normalised 1-D blur weights.
+ * top, left, bh, bw: the crop box.  post_mask: 0xFF (no posterize), 0xFE, 0xFC, 0xF8 or 0xF0.  sharpen: 0 or 1. */
+typedef struct svla_aug_transform {
+    int nops, ops_packed;
+    float f[4];
+    int nops_before_contrast;
+    float wx[5], wy[9];
+    int top, left, bh, bw;
+    int post_mask, sharpen;
+} svla_aug_transform;
+/* table_host: HOST pointer to the table (read during the call, like wx5 / wy9 above); table_dev: device scratch of the same size that the kernel reads.
+ * Every entry validates the whole host table first and then copies it to table_dev on the stream (hipMemcpyAsync) in front of its launch, so a kernel only
+ * ever reads a table that its own entry point has validated (three copies of G x 108 bytes per application; the scratch may be shared by the three calls).
+ * Refused with SVLA_EINVAL, nothing copied, nothing launched, y untouched: a box that leaves the image, nops > 4 or an unknown operation
+ * code, nops_before_contrast that is not the position of contrast, a post_mask outside the five above, sharpen outside {0, 1}, N % group_len != 0, H < 5,
+ * W < 3, group_len or N / group_len above 65535.  partials [N, 64] as svla_aug_gray_partials writes them; the rows of a group without contrast stay unwritten
+ * and unread. */
+int svla_aug_gray_partials_grouped(const unsigned char* x, int N, int H, int W, int group_len, const svla_aug_transform* table_host,
+                                   svla_aug_transform* table_dev, unsigned long long* partials, void* stream);
+int svla_aug_jitter_blur_grouped_u8(const unsigned char* x, unsigned char* y, int N, int H, int W, int group_len, const svla_aug_transform* table_host,
+                                    svla_aug_transform* table_dev, const unsigned long long* partials, void* stream);
+int svla_aug_resize_post_sharp_grouped_u8(const unsigned char* x, unsigned char* y, int N, int H, int W, int group_len, const svla_aug_transform* table_host,
+                                          svla_aug_transform* table_dev, void* stream);
+
 /* ---- camera frames -> the model's input size (SigLIP presets: 224 x 384 -> 256 x 256) ---------------------------------------------- */
 /* tensor_image_preprocessor prepends torchvision Resize(size, bicubic, antialias=True) when the size is not the camera's
  * (architecture/models/transformer_models/preprocessors.py:35-43); on the reference's device-resident uint8 frames that is

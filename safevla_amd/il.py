@@ -63,7 +63,7 @@ class EarlyFusionCnnTransformer(Tower):
 
     def __init__(self, device="cuda", max_length: int = 1000, input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"),
                  image_preprocessor=None, n_fusion_layers: int = 3, n_decoder_layers: int = 3, dino_dim: int = DINO, text_encoder: str = "t5-small", d_model: int = 512, n_heads: int = 8,
-                 n_heads_decoder: Optional[int] = None):
+                 n_heads_decoder: Optional[int] = None, data_augmentation: bool = False):
         if not torch.cuda.is_available():
             raise RuntimeError("safevla_amd needs an MI355X: there is no CPU or eager fallback for the policy kernels")
         ops.lib()
@@ -76,6 +76,14 @@ class EarlyFusionCnnTransformer(Tower):
         self.towers = [self]
         self.input_sensors = list(input_sensors)
         self.image_preprocessor = image_preprocessor
+        # data_augmentation (train_pl.py:92, early_fusion_tsfm_models.py:342-343: the random v2 list, preprocessors.py:86-118): forward(batch) passes each camera's
+        # uint8 frames [B,T,H,W,3] through that camera's augmenter -- one newly drawn transform per trajectory -- in front of the frozen trunk; the SigLIP presets
+        # augment at their 256 x 256 input size, behind the resize.  Seed a camera's draws through ``augmenters[cam].generator``.  Pre-encoded features pass untouched.
+        self.data_augmentation = bool(data_augmentation)
+        if self.data_augmentation:
+            from .preproc import RandomDataAugmenter
+            size = (256, 256) if text_encoder.startswith("SigLIP") else None
+            self.augmenters = [RandomDataAugmenter(size=size), RandomDataAugmenter(size=size)]
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self.sync_weights()
 
@@ -119,7 +127,7 @@ class EarlyFusionCnnTransformer(Tower):
 
     # ---- batch -> kernel inputs ----------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def prepare(self, batch: Dict) -> Prep:
+    def prepare(self, batch: Dict, augment: bool = False) -> Prep:
         dev = self.device_
         nav = batch[NAV]
         B, T = nav.shape[:2]
@@ -133,6 +141,8 @@ class EarlyFusionCnnTransformer(Tower):
             if x.dtype == torch.uint8:                           # raw frames [B,T,H,W,3] -> frozen ViT
                 if self.image_preprocessor is None:
                     self.image_preprocessor = self._frozen_image_encoder(key, dev)
+                if augment:
+                    x = self.augmenters[cam].augment_u8(x)
                 fr = x.transpose(0, 1).reshape(R, *x.shape[2:]).contiguous()
                 self.image_preprocessor.process_tokens(fr, p.tokens, cam)
             else:                                                # pre-encoded features [B,T,384,7,12]
@@ -172,7 +182,7 @@ class EarlyFusionCnnTransformer(Tower):
 
     # ---- reference forward API --------------------------------------------------------------------------------------------------
     def forward(self, batch: Dict) -> Dict[str, torch.Tensor]:
-        prep = self.prepare(batch)
+        prep = self.prepare(batch, augment=self.data_augmentation)
         logits, _, _ = _TowerFn.apply(self._anchor, self, prep, True, False)      # [T, B, A] fp32
         out = dict(actions_logits=logits.transpose(0, 1))
         if "actions" in batch:
@@ -184,9 +194,11 @@ class EarlyFusionCnnTransformer(Tower):
 
     @classmethod
     def build_agent(cls, model_version="small_3", input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"), loss="action", device="cuda",
-                    sampling="greedy", ckpt_pth: Optional[str] = None, **kw):
-        """``build_agent`` of early_fusion_tsfm_models.py:352-363: the model of ``build_model`` wrapped in its online agent."""
-        return EarlyFusionCnnTransformerAgent(cls.build_model(model_version, input_sensors, loss, device=device, ckpt_pth=ckpt_pth), device, sampling, **kw)
+                    sampling="greedy", data_augmentation: bool = False, ckpt_pth: Optional[str] = None, **kw):
+        """``build_agent`` of early_fusion_tsfm_models.py:352-363: the model of ``build_model`` wrapped in its online agent.  ``data_augmentation`` reaches the
+        model's forward(batch) only: the agent's single steps act on the frames as they come."""
+        return EarlyFusionCnnTransformerAgent(cls.build_model(model_version, input_sensors, loss, data_augmentation, device=device, ckpt_pth=ckpt_pth), device,
+                                              sampling, **kw)
 
     @classmethod
     def version_config(cls, model_version):
@@ -197,13 +209,13 @@ class EarlyFusionCnnTransformer(Tower):
 
     @classmethod
     def build_model(cls, model_version="small_3", input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"), loss="action",
-                    device="cuda", ckpt_pth: Optional[str] = None, ckpt_prefix: str = "model."):
+                    data_augmentation: bool = False, device="cuda", ckpt_pth: Optional[str] = None, ckpt_prefix: str = "model."):
         if model_version not in cls.VERSIONS:
             raise NotImplementedError(f"model_version {model_version!r}: built are {sorted(cls.VERSIONS)} (512-wide fusion transformer + llama decoder; "
                                       "early_fusion_tsfm_models.py:221-312)")
         nf, nd, dd, te, dm, nh, nhd = cls.version_config(model_version)
         m = cls(device=device, input_sensors=input_sensors, n_fusion_layers=nf, n_decoder_layers=nd, dino_dim=dd, text_encoder=te, d_model=dm, n_heads=nh,
-                n_heads_decoder=nhd)
+                n_heads_decoder=nhd, data_augmentation=data_augmentation)
         if ckpt_pth is not None:    # Lightning checkpoint (training/offline/train_utils.py:6-68)
             sd = torch.load(ckpt_pth, map_location="cpu")["state_dict"]
             m.load_state_dict({k[len(ckpt_prefix):]: v for k, v in sd.items() if k.startswith(ckpt_prefix)}, strict=False)

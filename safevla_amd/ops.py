@@ -764,6 +764,76 @@ def aug_resize_post_sharp(x_u8, box=None, posterize=False, sharpen=False, out=No
     return y
 
 
+# per-trajectory random frame augmentation (csrc/augment_grouped.hip): the three launches above with one transform per group of frames
+class AugTransform(ctypes.Structure):
+    """svla_aug_transform of include/svla.h: one entry of the table"""
+    _fields_ = [("nops", ctypes.c_int), ("ops_packed", ctypes.c_int), ("f", ctypes.c_float * 4), ("nops_before_contrast", ctypes.c_int),
+                ("wx", ctypes.c_float * 5), ("wy", ctypes.c_float * 9), ("top", ctypes.c_int), ("left", ctypes.c_int), ("bh", ctypes.c_int), ("bw", ctypes.c_int),
+                ("post_mask", ctypes.c_int), ("sharpen", ctypes.c_int)]
+
+
+class AugTable:
+    """G transforms as the grouped launches take them: the host table (a ctypes array of AugTransform) and its device scratch.  ``entries``: one
+    (ops, factors, wx, wy, box, post_mask, sharpen) per group -- ops / factors as aug_jitter_blur takes them, box = (top, left, height, width).  Nothing is checked
+    here: the C entry points validate every entry before they enqueue anything.  Every launch uploads the table it has just validated to ``dev`` in front of itself."""
+
+    def __init__(self, entries, device):
+        self.host = (AugTransform * len(entries))()
+        for t, (ops, factors, wx, wy, box, post_mask, sharpen) in zip(self.host, entries):
+            n, packed, f = _aug_ops(ops, factors)
+            ops = [int(o) for o in ops]
+            t.nops, t.ops_packed, t.f = n, packed, (ctypes.c_float * 4)(*f)
+            t.nops_before_contrast = ops.index(AUG_CONTRAST) if AUG_CONTRAST in ops else -1
+            t.wx, t.wy = (ctypes.c_float * 5)(*[float(v) for v in wx]), (ctypes.c_float * 9)(*[float(v) for v in wy])
+            t.top, t.left, t.bh, t.bw = [int(v) for v in box]
+            t.post_mask, t.sharpen = int(post_mask), int(bool(sharpen))
+        self.dev = torch.empty(max(1, len(entries)) * ctypes.sizeof(AugTransform), device=device, dtype=torch.uint8)
+
+    def __len__(self):
+        return len(self.host)
+
+    def args(self):
+        """(host pointer, device scratch pointer) as the entry points take them"""
+        return ctypes.cast(self.host, ctypes.c_void_p), _p(self.dev)
+
+
+def _aug_grouped_frames(x_u8, table, group_len):
+    N, H, W = _aug_frames(x_u8)
+    group_len = int(group_len)
+    if group_len >= 1 and N % group_len == 0 and len(table) != N // group_len:      # (the C entry would read a shorter table past its end; what else is wrong it refuses itself)
+        raise ValueError(f"{N} frames in groups of {group_len} need {N // group_len} table entries, got {len(table)}")
+    return N, H, W, group_len
+
+
+def aug_gray_partials_grouped(x_u8, table: AugTable, group_len):
+    """aug_gray_partials with one transform per group: partial sums [N, AUG_NPART] of gray(x) after the operations that precede contrast in the group's order; the rows
+    of a group without contrast stay unwritten"""
+    N, H, W, group_len = _aug_grouped_frames(x_u8, table, group_len)
+    part = torch.empty(N, AUG_NPART, device=x_u8.device, dtype=torch.int64)
+    lib().call("svla_aug_gray_partials_grouped", _p(x_u8), N, H, W, group_len, *table.args(), _p(part), _stream())
+    return part
+
+
+def aug_jitter_blur_grouped(x_u8, table: AugTable, group_len, partials, out=None):
+    """aug_jitter_blur with one transform per group (ColorJitter in the group's order, then its 5 x 9 blur) -- one launch"""
+    N, H, W, group_len = _aug_grouped_frames(x_u8, table, group_len)
+    y = torch.empty_like(x_u8) if out is None else out
+    _aug_frames(y, "out")
+    assert y.shape == x_u8.shape
+    lib().call("svla_aug_jitter_blur_grouped_u8", _p(x_u8), _p(y), N, H, W, group_len, *table.args(), _p(partials), _stream())
+    return y
+
+
+def aug_resize_post_sharp_grouped(x_u8, table: AugTable, group_len, out=None):
+    """aug_resize_post_sharp with one transform per group (its crop box resized to the frame, x & its post_mask, its sharpness) -- one launch"""
+    N, H, W, group_len = _aug_grouped_frames(x_u8, table, group_len)
+    y = torch.empty_like(x_u8) if out is None else out
+    _aug_frames(y, "out")
+    assert y.shape == x_u8.shape
+    lib().call("svla_aug_resize_post_sharp_grouped_u8", _p(x_u8), _p(y), N, H, W, group_len, *table.args(), _stream())
+    return y
+
+
 def resize_bicubic_aa_u8(x_u8, out_hw, out=None):
     """u8 [B,H,W,3] -> u8 [B,OH,OW,3]: torchvision's Resize(out_hw, bicubic, antialias=True) as it acts on device-resident uint8 frames (fp32 interpolation, clamp,
     round half to even; csrc/resize.hip) -- one launch.  Equal sizes: an exact copy.  The kernel's limits (sizes >= 4, per-axis scale in [1/4, 4]) are the C entry's:

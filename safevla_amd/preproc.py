@@ -108,6 +108,11 @@ def crop_box(H: int, W: int, scale: float, generator: Optional[torch.Generator] 
                 top = int(torch.randint(0, H - h + 1, (1,), generator=generator).item())
                 left = int(torch.randint(0, W - w + 1, (1,), generator=generator).item())
                 return top, left, h, w
+    return crop_fallback_box(H, W, ratio)
+
+
+def crop_fallback_box(H: int, W: int, ratio=CROP_RATIO) -> Tuple[int, int, int, int]:
+    """RandomResizedCrop's centre crop when no attempt of the search fits: the whole frame clipped to the nearer end of ``ratio``"""
     in_ratio = float(W) / float(H)
     if in_ratio < min(ratio):
         w = W
@@ -166,6 +171,103 @@ def apply_augment_u8(x: torch.Tensor, call: AugmentCall, debug: bool = False, ou
         x = ops.aug_resize_post_sharp(x, sharpen=True)
     stages.append(("sharpness", x))
     return stages
+
+
+# ---- the full random v2 list, per trajectory (imitation-learning training from raw frames) ----------------------------------------------------
+# The IL Preprocessor (architecture/models/transformer_models/preprocessors.py:86-118) builds tensor_image_preprocessor(data_augmentation=True) with specific=False
+# (:22-60): the random v2 list of utils/transformation_util.py:12-28 itself, applied once per trajectory and camera to that trajectory's [T, 3, H, W] frames.  Every
+# call draws everything anew -- ColorJitter order and factors, blur sigma, a crop box with its own scale, four posterize coins (7, 6, 5, 4 bits), one sharpness coin.
+CROP_SCALE = (0.9, 1.0)
+POSTERIZE_BITS = (7, 6, 5, 4)
+
+
+class RandomAugmentCall(NamedTuple):
+    """one call of the random v2 list: what it drew, in the form the grouped kernels take"""
+    order: Tuple[int, int, int, int]
+    brightness: float
+    contrast: float
+    saturation: float
+    hue: float
+    sigma: float
+    box: Tuple[int, int, int, int]
+    post_mask: int
+    sharpen: bool
+
+    def factor(self, op: int) -> float:
+        return (self.brightness, self.contrast, self.saturation, self.hue)[op]
+
+    def as_augment_call(self) -> AugmentCall:
+        """the same transform for the single-transform path (apply_augment_u8), which knows posterize to 7 bits only"""
+        assert self.post_mask in (0xFF, 0xFE), f"apply_augment_u8 cannot express post_mask {self.post_mask:#x}"
+        p = AugmentParams(self.brightness, self.saturation, self.hue, self.contrast, self.sigma, 1.0, (int(self.post_mask == 0xFE), 0, 0, 0), int(self.sharpen))
+        return AugmentCall(p, self.order, self.box)
+
+
+def posterize_mask(coins) -> int:
+    """the chain RandomPosterize(7), (6), (5), (4) with the coins that came up: x & m7 & m6 ... = x & (0xFF << (8 - the fewest bits drawn)); none drawn: 0xFF"""
+    bits = [b for b, c in zip(POSTERIZE_BITS, coins) if c]
+    return (0xFF << (8 - min(bits))) & 0xFF if bits else 0xFF
+
+
+def sample_random_augment_call(H: int, W: int, generator: Optional[torch.Generator] = None, ratio=CROP_RATIO) -> RandomAugmentCall:
+    """The per-call draws of the random v2 list on a torch generator, in Compose order (torchvision is not installed here: this sequence is the contract, PARITY
+    UNPINNED like the sampler above).  ColorJitter: randperm(4), then brightness, contrast, saturation, hue.  GaussianBlur: sigma.  RandomResizedCrop: up to ten
+    attempts, each drawing a scale and a log-uniform ratio (both consumed whether or not the attempt can fit), top and left on success, else the centre-crop
+    fallback.  RandomPosterize x 4: one coin each for 7, 6, 5, 4 bits.  RandomAdjustSharpness: one coin."""
+    g = generator
+    u = lambda lo, hi: torch.empty(1).uniform_(lo, hi, generator=g).item()
+    order = tuple(int(v) for v in torch.randperm(4, generator=g).tolist())
+    brightness, contrast, saturation, hue = u(0.6, 1.4), u(0.6, 1.4), u(0.8, 1.2), u(-0.05, 0.05)
+    sigma = u(0.1, 2.0)
+    box = None
+    lo, hi = math.log(ratio[0]), math.log(ratio[1])
+    for _ in range(10):
+        target = H * W * u(*CROP_SCALE)
+        ar = math.exp(u(lo, hi))
+        w, h = int(round(math.sqrt(target * ar))), int(round(math.sqrt(target / ar)))
+        if 0 < w <= W and 0 < h <= H:
+            top = int(torch.randint(0, H - h + 1, (1,), generator=g).item())
+            left = int(torch.randint(0, W - w + 1, (1,), generator=g).item())
+            box = (top, left, h, w)
+            break
+    if box is None:
+        box = crop_fallback_box(H, W, ratio)
+    coins = [bool(torch.rand(1, generator=g).item() < 0.2) for _ in POSTERIZE_BITS]
+    sharpen = bool(torch.rand(1, generator=g).item() < 0.5)
+    return RandomAugmentCall(order, brightness, contrast, saturation, hue, sigma, box, posterize_mask(coins), sharpen)
+
+
+def apply_random_augment_u8(x: torch.Tensor, calls, group_len: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """u8 [N,H,W,3] -> u8 [N,H,W,3]: frame n gets ``calls[n // group_len]`` (RandomAugmentCall) -- ColorJitter in that call's order, its blur, its crop + resize, its
+    posterize mask, its sharpness.  Three launches (each uploads the table it validated) whatever len(calls) is; per frame bit for bit what apply_augment_u8 computes with the same
+    transform.  A refused table (ops.aug_*_grouped) raises before anything is launched: ``out`` stays untouched."""
+    table = ops.AugTable([(c.order, [c.factor(o) for o in c.order], gaussian_weights(5, c.sigma), gaussian_weights(9, c.sigma), c.box, c.post_mask, c.sharpen)
+                          for c in calls], x.device)
+    part = ops.aug_gray_partials_grouped(x, table, group_len)
+    y = ops.aug_jitter_blur_grouped(x, table, group_len, part)
+    return ops.aug_resize_post_sharp_grouped(y, table, group_len, out=out)
+
+
+class RandomDataAugmenter:
+    """The IL Preprocessor's frame augmentation (preprocessors.py:101-118) for one camera: ``augment_u8`` draws one random call per trajectory of a
+    [B, T, H, W, 3] uint8 batch and applies the B transforms in one grouped application (group = trajectory).  ``size``: the model's input size when it is not the
+    camera's (the SigLIP presets' (256, 256)): the antialiased bicubic resize runs first and the list acts at the resized geometry, as the reference builds it
+    with ``size``.  ``generator``: torch generator of the draws; None = the CPU default.  ``last_calls``: the calls of the latest batch."""
+
+    def __init__(self, size: Optional[Tuple[int, int]] = None, generator: Optional[torch.Generator] = None):
+        self.size = None if size is None else (int(size[0]), int(size[1]))
+        self.generator = generator
+        self.last_calls = []
+
+    def augment_u8(self, frames_u8: torch.Tensor) -> torch.Tensor:
+        assert frames_u8.dtype == torch.uint8 and frames_u8.dim() == 5 and frames_u8.shape[-1] == 3, f"uint8 [B,T,H,W,3] frames; got {tuple(frames_u8.shape)}"
+        B, T = frames_u8.shape[:2]
+        x = frames_u8.reshape(B * T, *frames_u8.shape[2:]).contiguous()
+        if self.size is not None and tuple(x.shape[1:3]) != self.size:
+            x = ops.resize_bicubic_aa_u8(x, self.size)
+        H, W = x.shape[1:3]
+        self.last_calls = [sample_random_augment_call(H, W, self.generator) for _ in range(B)]
+        return apply_random_augment_u8(x, self.last_calls, T).view(B, T, H, W, 3)
 
 
 class DataAugmentationPreprocessor:
@@ -235,16 +337,19 @@ class SigLIPDataAugmentationPreprocessor(DataAugmentationPreprocessor):
 
     ``augment_u8`` makes this class an ``augmenter=`` of ``SigLIPPreprocessor``, whose own input stays 256 x 256.
 
-    Not reproduced: the reference's online SigLIP class draws the FULL random v2 list afresh on every call, including its four-step posterize chain with bits 7 to
-    4.  The kernels here implement the sampled-specific list (one transform kept for ``num_steps_to_change`` calls, posterize to 7 bits), as the DINOv2
-    preprocessor's augmentation does."""
+    ``random_per_call=True`` (with ``use_augmentation``) is the reference's online SigLIP class as written: the FULL random v2 list drawn afresh on every call,
+    including its four-step posterize chain with bits 7 to 4 -- one ``sample_random_augment_call`` per ``process`` / ``augment_u8``, applied to the whole batch as one
+    group (the grouped launches with G = 1).  The default keeps the sampled-specific list (one transform kept for ``num_steps_to_change`` calls, posterize to 7
+    bits), as the DINOv2 preprocessor's augmentation does."""
 
     def __init__(self, rgb_input_uuid: str, output_uuid: str, device="cuda", height=224, width=384, size=(256, 256), mean=SIGLIP_RGB_MEANS, stdev=SIGLIP_RGB_STDS,
-                 normalize=True, use_augmentation=False, num_steps_to_change=500, generator: Optional[torch.Generator] = None, **kw):
+                 normalize=True, use_augmentation=False, num_steps_to_change=500, generator: Optional[torch.Generator] = None, random_per_call=False, **kw):
         super().__init__(rgb_input_uuid, output_uuid, device=device, normalize=normalize, mean=mean, stdev=stdev, height=height, width=width,
                          use_augmentation=use_augmentation, num_steps_to_change=num_steps_to_change, generator=generator)
         self.size = (int(size[0]), int(size[1]))
         self.observation_space = Box(-float("inf"), float("inf"), (*self.size, 3))
+        self.random_per_call = bool(random_per_call)
+        self.last_random_call: Optional[RandomAugmentCall] = None
 
     def augment_u8(self, frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """u8 [B,H,W,3] -> u8 [B,*size,3]: resize when the size differs, then (use_augmentation) the sampled transform, which counts as one call of the schedule"""
@@ -259,9 +364,13 @@ class SigLIPDataAugmentationPreprocessor(DataAugmentationPreprocessor):
             return out
         if resize:
             x = ops.resize_bicubic_aa_u8(x, self.size)
+        if self.random_per_call:
+            self.last_random_call = sample_random_augment_call(*self.size, self.generator)
+            return apply_random_augment_u8(x, [self.last_random_call], x.shape[0], out=out)
         return apply_augment_u8(x, self.next_call(*self.size), out=out)
 
     def augment_u8_stages(self, frames_u8: torch.Tensor):
+        assert not self.random_per_call, "the stage-by-stage debug form exists for the sampled-specific transform only"
         x = self._frames(frames_u8)
         if tuple(x.shape[1:3]) != self.size:
             x = ops.resize_bicubic_aa_u8(x, self.size)

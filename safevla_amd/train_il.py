@@ -61,12 +61,18 @@ def main():
     ap.add_argument("--goal_tokens", type=int, default=12)
     ap.add_argument("--raw_frames", action="store_true")
     ap.add_argument("--frame_hw", type=int, nargs=2, default=None, metavar=("H", "W"), help="size of the synthetic --raw_frames (default: the preset's own input size)")
+    ap.add_argument("--data_augmentation", action="store_true",
+                    help="with --raw_frames: the random v2 frame augmentation, one newly drawn transform per trajectory and camera (the reference trains with it on "
+                         "unless --no_augmentation, train_pl.py:92; off here unless asked for)")
     ap.add_argument("--init_ckpt", default=None)
     args = ap.parse_args()
     rank, local, world = parallel.init_from_env()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    model = EarlyFusionCnnTransformer.build_model(args.model_version, args.input_sensors, args.loss, device=dev, ckpt_pth=args.init_ckpt)
+    model = EarlyFusionCnnTransformer.build_model(args.model_version, args.input_sensors, args.loss, args.data_augmentation, device=dev, ckpt_pth=args.init_ckpt)
+    if args.data_augmentation:
+        for cam, a in enumerate(model.augmenters):
+            a.generator = torch.Generator().manual_seed(4321 + 2 * rank + cam)
     if world > 1:
         torch.distributed.broadcast(model.arena.flat_p, src=0)
         model.sync_weights()
