@@ -175,6 +175,22 @@ int svla_attn_bwd_bf16(const svla_bf16* Q, const svla_bf16* K, const svla_bf16* 
  * order instead of whole rows per XCD (tools/attn_bwd_once.py: the mapping is worth 1.4 %); 4 = single-query forwards (Sq == 1 without bias / trajectory mask /
  * dropout: the KV-cached acting step) on the tile kernels instead of the decode kernel that reads only the valid keys.  Bits combine. */
 int svla_attn_bwd_two_pass(int on);
+/* Last fusion layer with the K / V projections absorbed into its single query (allenact_dino_transformer.py:545-552, 708: nn.MultiheadAttention of which only
+ * x[:, 0] is consumed), 8 heads of 64, S <= 256 (csrc/attn_q1.hip).  X: the layer's input tokens, row r at X + r*ldx, [S, 512]; QT [R, 8, 512]: row (r, h) =
+ * W_k,h^T q_h.  Forward: P [R, 8, S] = softmax_j(scale * QT_h . x_j) (fp32, saved for the backward), C [R, 8, 512] = sum_j pd_hj x_j and SIG [R, 8] = sum_j pd_hj
+ * with pd = keep / (1 - p) * P; the keep decision of (r, h, key j) is that of svla_attn_fwd_bf16 with Sq = 1 on the same S.  The caller finishes
+ * o_h = W_v,h C_h + SIG_h b_v,h.  Backward (same citation): DC [R, 8, 512] = W_v,h^T do_h, DSIG [R, 8] = do_h . b_v,h -> DX [R, S, 512] (row stride lddx, EVERY
+ * token written) and DQT [R, 8, 512] = dS X.  X is read from HBM once per call; no atomics: bitwise repeatable. */
+int svla_attn_q1_fwd_bf16(const svla_bf16* X, long ldx, const svla_bf16* QT, svla_bf16* C, float* SIG, float* P, int R, int S, float scale,
+                          const svla_dropout* drop, void* stream);
+int svla_attn_q1_bwd_bf16(const svla_bf16* X, long ldx, const svla_bf16* QT, const svla_bf16* DC, const float* DSIG, const float* P,
+                          svla_bf16* DX, long lddx, svla_bf16* DQT, int R, int S, float scale, const svla_dropout* drop, void* stream);
+/* Head-expanded operands of the products around them (allenact_dino_transformer.py:545-552, 708: the per-head blocks of in_proj_weight): E [8 R, 512], row
+ * r*8 + h = v[r] with the columns outside [64 h, 64 h + 64) zeroed.  Optional by-products: dot [R, 8] = v_h . bias_h (with bias [512]); vs [R, 512] =
+ * sigma[r, h] * v[r, 64 h + d] (with sigma [R, 8]).  svla_head_pick_bf16 reads the diagonal blocks back: out[r, 64 h + d] = G[r*8 + h, 64 h + d]
+ * (+ sigma[r, h] * bias[64 h + d] when sigma is given). */
+int svla_head_expand_bf16(const svla_bf16* v, long ldv, int R, svla_bf16* E, const float* bias, float* dot, const float* sigma, svla_bf16* vs, void* stream);
+int svla_head_pick_bf16(const svla_bf16* G, int R, const float* sigma, const float* bias, svla_bf16* out, long ldo, void* stream);
 
 /* ---- recorded launch sequences --------------------------------------------------------------------------------------------------
  * The single-step acting forward (the reference's rollout collection calls DinoLLAMATxNavActorCritic.forward once per env step,

@@ -169,6 +169,9 @@ class Tower(nn.Module):
         self.max_steps = max_steps
         self.time_step_counter = 0
         self.prune_last = True      # dead-output elimination in the last fusion layer (exact; see run_forward)
+        # pruned last layer of an update pass: K / V projections absorbed into its single query, K and V never materialised (csrc/attn_q1.hip; run_forward).
+        # SVLA_LAST_LAYER_KV=1 keeps the materialised K / V path (A/B)
+        self.absorb_last = _os0.environ.get("SVLA_LAST_LAYER_KV", "0") != "1"
         # BASELINE config 5 ("fp8 MFMA attention"): the full-sequence fusion-encoder attention layers run on the e4m3 / e5m2 kernels
         # (svla_attn_fp8_*); the pruned last layer (one query per row) and the decoder keep the bf16 kernels.  bf16 precision only.
         self.fp8_attention = False
@@ -383,19 +386,32 @@ class Tower(nn.Module):
         for i, l in enumerate(ve.fusion_xformer.layers):
             if i == nfl - 1 and self.prune_last:
                 # Only sequence position 0 of the last fusion layer is consumed (allenact_dino_transformer.py:708 x[:, 0]):
-                # K/V are still projected for all tokens, but Q / attention / out_proj / norm1 / FFN / norm2 run on the R
-                # position-0 rows only.  Identical outputs and gradients; ~84 % less work in this layer.
+                # Q / attention / out_proj / norm1 / FFN / norm2 run on the R position-0 rows only; K/V still cover all tokens (projected in full, or
+                # absorbed into the query: below).  Identical outputs and gradients; ~84 % less work in this layer.
                 b_in = l.self_attn.in_proj_bias
-                kv = ops.gemm_nt(xf, w[f"f{i}.in"][D:], M, 2 * D, D, bias=b_in[D:])
                 q0 = ops.gemm_nt(xf, w[f"f{i}.in"][:D], R, D, D, bias=b_in[:D], lda=S * D)
-                ao, lse = ops.attn_fwd(q0, kv, kv[:, D:], 2 * D, R, S, H, SCF, save_lse=need_grad, Sq=1, ldq=D, drop=site(i, 0), head_dim=self.hdim)
+                # Update passes on the bf16 path: with one query per (row, head) the K and V projections move onto the query side exactly --
+                # qt_h = W_k,h^T q_h scores the raw tokens (the K bias shifts every score of a head alike: the softmax drops it), c_h = sum_j pd_hj x_j,
+                # o_h = W_v,h c_h + (sum_j pd_hj) b_v,h -- so K / V for all M tokens are never computed or kept.  The per-head products are plain GEMMs over
+                # head-expanded [8 R, 512] rows.  Acting steps, fp32 verification mode and absorb_last = False take the materialised branch below.
+                absorbed = need_grad and self.absorb_last and self.adt == BF16 and self.hdim == 64 and H == 8 and S <= 256
+                if absorbed:
+                    eq, _, _ = ops.head_expand(q0, R)
+                    qt = ops.gemm_nt(eq, self._wt[f"f{i}.in"][:, D:2 * D], 8 * R, D, D)
+                    cc, sig, prob = ops.attn_q1_fwd(xf, S * D, qt, R, S, SCF, drop=site(i, 0))
+                    ao = ops.head_pick(ops.gemm_nt(cc, w[f"f{i}.in"][2 * D:], 8 * R, D, D), R, sigma=sig, bias=b_in[2 * D:])
+                    att = dict(absorbed=True, eq=eq, qt=qt, cc=cc, sig=sig, prob=prob)
+                else:
+                    kv = ops.gemm_nt(xf, w[f"f{i}.in"][D:], M, 2 * D, D, bias=b_in[D:])
+                    ao, lse = ops.attn_fwd(q0, kv, kv[:, D:], 2 * D, R, S, H, SCF, save_lse=need_grad, Sq=1, ldq=D, drop=site(i, 0), head_dim=self.hdim)
+                    att = dict(absorbed=False, kv=kv, lse=lse)
                 h1 = ops.gemm_nt(ao, w[f"f{i}.out"], R, D, D, bias=l.self_attn.out_proj.bias, residual=xf, ldr=S * D, drop=site(i, 1, S))
                 x1, m1, r1 = ops.norm_fwd(h1, l.norm1.weight, l.norm1.bias, 1e-5, R, save_stats=need_grad, D=D)
                 f1 = ops.gemm_nt(x1, w[f"f{i}.l1"], R, 2048, D, bias=l.linear1.bias, act=ops.ACT_RELU, drop=site(i, 2, S))
                 h2 = ops.gemm_nt(f1, w[f"f{i}.l2"], R, D, 2048, bias=l.linear2.bias, residual=x1, drop=site(i, 3, S))
                 xo, m2, r2 = ops.norm_fwd(h2, l.norm2.weight, l.norm2.bias, 1e-5, R, save_stats=need_grad, D=D)
                 if need_grad:
-                    fl.append(dict(pruned=True, x=xf, kv=kv, q0=q0, ao=ao, lse=lse, h1=h1, x1=x1, n1=(m1, r1), f1=f1, h2=h2, n2=(m2, r2)))
+                    fl.append(dict(pruned=True, x=xf, q0=q0, ao=ao, **att, h1=h1, x1=x1, n1=(m1, r1), f1=f1, h2=h2, n2=(m2, r2)))
                 xf, xf_stride = xo, D
                 continue
             qkv = ops.gemm_nt(xf, w[f"f{i}.in"], M, 3 * D, D, bias=l.self_attn.in_proj_bias)
@@ -624,15 +640,30 @@ class Tower(nn.Module):
                 da = dh1 if da is None else da
                 ops.gemm_tn_acc(da, a["ao"], dw[f"f{i}.out"], R, D, D, db=g(l.self_attn.out_proj.bias))
                 dao = ops.gemm_nt(da, wt[f"f{i}.out"], R, D, D)
-                dq0 = torch.empty(R, D, device=dev, dtype=self.adt)
-                dkv = torch.empty(M, 2 * D, device=dev, dtype=self.adt)
-                kv = a["kv"]
-                ops.attn_bwd(a["q0"], kv, kv[:, D:], 2 * D, a["ao"], D, a["lse"], dao, D, dq0, dkv, dkv[:, D:], 2 * D, R, S, H, SCF, head_dim=self.hdim,
-                             Sq=1, ldq=D, lddq=D, drop=site(i, 0))
                 gb = g(l.self_attn.in_proj_bias)
-                ops.gemm_tn_acc(dkv, a["x"], dw[f"f{i}.in"][D:], M, 2 * D, D, db=gb[D:])
-                ops.gemm_tn_acc(dq0, a["x"], dw[f"f{i}.in"][:D], R, D, D, ldx=S * D, db=gb[:D])
-                dyf = ops.gemm_nt(dkv, wt[f"f{i}.in"][:, D:], M, D, 2 * D)                       # dX through K and V, all tokens
+                if a["absorbed"]:
+                    # backward of the absorbed form (run_forward): dc_h = W_v,h^T do_h, dsigma_h = do_h . b_v,h; the streaming kernel returns dX of every token
+                    # and dqt; every weight gradient goes through the accumulating GEMM / column sum (deterministic mode included).  The K third of the bias
+                    # gradient is exactly zero (sum_j dS_hj = 0) and is not touched.
+                    w_in, wt_in, dw_in = w[f"f{i}.in"], wt[f"f{i}.in"], dw[f"f{i}.in"]
+                    edao, dsig, sdao = ops.head_expand(dao, R, bias=l.self_attn.in_proj_bias[2 * D:], sigma=a["sig"])
+                    dcc = ops.gemm_nt(edao, wt_in[:, 2 * D:], 8 * R, D, D)
+                    ops.gemm_tn_acc(edao, a["cc"], dw_in[2 * D:], 8 * R, D, D)                   # dW_v,h += do_h c_h^T
+                    ops.colsum_acc(sdao, gb[2 * D:], R, D)                                       # db_v,h += sigma_h do_h
+                    dyf, dqt = ops.attn_q1_bwd(a["x"], S * D, a["qt"], dcc, dsig, a["prob"], R, S, SCF, drop=site(i, 0))
+                    dyf = dyf.view(M, D)
+                    ops.gemm_tn_acc(a["eq"], dqt, dw_in[D:2 * D], 8 * R, D, D)                   # dW_k,h += q_h dqt_h^T
+                    dq0 = ops.head_pick(ops.gemm_nt(dqt, w_in[D:2 * D], 8 * R, D, D), R)         # W_k,h dqt_h
+                    ops.gemm_tn_acc(dq0, a["x"], dw_in[:D], R, D, D, ldx=S * D, db=gb[:D])
+                else:
+                    dq0 = torch.empty(R, D, device=dev, dtype=self.adt)
+                    dkv = torch.empty(M, 2 * D, device=dev, dtype=self.adt)
+                    kv = a["kv"]
+                    ops.attn_bwd(a["q0"], kv, kv[:, D:], 2 * D, a["ao"], D, a["lse"], dao, D, dq0, dkv, dkv[:, D:], 2 * D, R, S, H, SCF, head_dim=self.hdim,
+                                 Sq=1, ldq=D, lddq=D, drop=site(i, 0))
+                    ops.gemm_tn_acc(dkv, a["x"], dw[f"f{i}.in"][D:], M, 2 * D, D, db=gb[D:])
+                    ops.gemm_tn_acc(dq0, a["x"], dw[f"f{i}.in"][:D], R, D, D, ldx=S * D, db=gb[:D])
+                    dyf = ops.gemm_nt(dkv, wt[f"f{i}.in"][:, D:], M, D, 2 * D)                   # dX through K and V, all tokens
                 t0 = ops.gemm_nt(dq0, wt[f"f{i}.in"][:, :D], R, D, D, residual=dh1)             # position 0: Q path + residual path
                 ops.rows_add(dyf, S * D, t0, D, R, D)
                 c["fusion"][i] = None

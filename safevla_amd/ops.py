@@ -492,6 +492,49 @@ def attn_bwd(q, k, v, ld, o, ldo, lse, do, lddo, dq, dk, dv, ldd, rows, S, H, sc
                rows, S, H, int(head_dim), float(scale), mask_mode, _p(traj), _p(bias), _p(kvalid), int(Sq), int(ldq), int(lddq), _p(d_ws), _d(drop), _stream())
 
 
+# ---- last fusion layer: K / V projections absorbed into the single query (csrc/attn_q1.hip) ---------------------------------------
+def attn_q1_fwd(x, ldx, qt, R, S, scale, drop=None):
+    """x: bf16 tokens, row r at element r * ldx, [S, 512]; qt [8 R, 512] (row r*8 + h = W_k,h^T q_h).  Returns c [8 R, 512] bf16, sigma [R, 8] fp32 and the
+    probabilities P [R, 8, S] fp32 that ``attn_q1_bwd`` reads."""
+    _chk(x, BF16, "x")
+    _chk(qt, BF16, "qt")
+    c = torch.empty(8 * R, 512, device=x.device, dtype=BF16)
+    sig = torch.empty(R, 8, device=x.device, dtype=F32)
+    P = torch.empty(R, 8, S, device=x.device, dtype=F32)
+    lib().call("svla_attn_q1_fwd_bf16", _p(x), int(ldx), _p(qt), _p(c), _p(sig), _p(P), R, S, float(scale), _d(drop), _stream())
+    return c, sig, P
+
+
+def attn_q1_bwd(x, ldx, qt, dc, dsig, P, R, S, scale, drop=None):
+    """Gradients of ``attn_q1_fwd``: dx [R, S, 512] bf16 (every token written) and dqt [8 R, 512] bf16."""
+    for t, n in ((x, "x"), (qt, "qt"), (dc, "dc")):
+        _chk(t, BF16, n)
+    dx = torch.empty(R, S, 512, device=x.device, dtype=BF16)
+    dqt = torch.empty(8 * R, 512, device=x.device, dtype=BF16)
+    lib().call("svla_attn_q1_bwd_bf16", _p(x), int(ldx), _p(qt), _p(dc), _p(dsig), _p(P),
+               _p(dx), S * 512, _p(dqt), R, S, float(scale), _d(drop), _stream())
+    return dx, dqt
+
+
+def head_expand(v, R, bias=None, sigma=None, ldv=None):
+    """E [8 R, 512]: row r*8 + h = v[r] with the columns outside head h's 64 zeroed.  With ``bias`` [512] also dot [R, 8] = v_h . bias_h; with ``sigma`` [R, 8] also
+    vs [R, 512] = sigma[r, h] * v[r, 64 h + d].  Returns (E, dot, vs)."""
+    _chk(v, BF16, "v")
+    E = torch.empty(8 * R, 512, device=v.device, dtype=BF16)
+    dot = torch.empty(R, 8, device=v.device, dtype=F32) if bias is not None else None
+    vs = torch.empty(R, 512, device=v.device, dtype=BF16) if sigma is not None else None
+    lib().call("svla_head_expand_bf16", _p(v), ldv if ldv is not None else v.stride(-2), R, _p(E), _p(bias), _p(dot), _p(sigma), _p(vs), _stream())
+    return E, dot, vs
+
+
+def head_pick(G, R, sigma=None, bias=None):
+    """out[r, 64 h + d] = G[r*8 + h, 64 h + d] (+ sigma[r, h] * bias[64 h + d]): the diagonal blocks of a product over head-expanded rows."""
+    _chk(G, BF16, "G")
+    out = torch.empty(R, 512, device=G.device, dtype=BF16)
+    lib().call("svla_head_pick_bf16", _p(G), R, _p(sigma), _p(bias), _p(out), 512, _stream())
+    return out
+
+
 # ---- deterministic gradient accumulation ---------------------------------------------------------------------------------------
 _DET_SLOTS = [None, None]
 
