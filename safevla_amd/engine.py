@@ -75,8 +75,6 @@ class PPOLagEngine:
         self.gemm_flops = 0
         # deterministic mode: an int64 shadow of the flat gradient buffer (8 B per parameter)
         self._det_shadow = torch.zeros(model.arena.flat_g.numel(), device=dev, dtype=torch.int64) if cfg.deterministic else None
-        if not hasattr(model, "_invalidate_hooks"):
-            model._invalidate_hooks = []
         # load_state_dict / broadcast replace the frozen encoder's tensors: recorded env-chunks must go.  The hook holds the engine weakly --
         # a strong reference to the cache would keep a discarded engine's recorded chunks (and their towers' activations) alive
         ref = weakref.ref(self)
@@ -123,7 +121,7 @@ class PPOLagEngine:
                 if plan is None:
                     continue
                 s_ = m._tower_streams[k]
-                m.towers[k]._seed_dev_buf.add_(0x3C6EF35)          # fresh dropout noise for this pass (forward and backward read the same seed)
+                m.towers[k].advance_device_seed()          # fresh dropout noise for this pass (forward and backward read the same seed)
                 s_.wait_stream(main)
                 plan.replay()
                 if last and parallel.is_dist():
@@ -174,24 +172,16 @@ class PPOLagEngine:
                 dfl = dfl.view(T, Bc, -1)
             tw.run_backward(prep, c, None, dv, dfl)
 
-        blocks = [actor_block if "ppo_log_loss" in names else None,
-                  critic_block if (("ppo_log_loss" in names and not discrete) or "ppo_value_loss" in names) else None,
-                  c_critic_block if ("safe_ppo_value_loss" in names or ("ppo_log_loss" in names and discrete)) else None]
+        blocks = [b if on else None for b, on in zip((actor_block, critic_block, c_critic_block), self.active_towers())]
         def run_block(k, t):
             if blocks[k] is None:
                 return None
             plan = None
             if record:
-                if getattr(t, "_seed_dev_buf", None) is None:
-                    t._seed_dev_buf = torch.tensor([(t.drop_seed_base * 0x9E3779B1) & 0x7FFFFFFF], device=m.device_, dtype=torch.int32)
-                t._seed_dev_buf.add_(0x3C6EF35)
-                t._seed_dev = t._seed_dev_buf          # dropout descriptors of the recorded pass point at the device-resident seed
+                t.advance_device_seed()
                 plan = ops.LaunchPlan()
-                try:
-                    with plan:
-                        blocks[k]()
-                finally:
-                    t._seed_dev = None
+                with t.device_resident(), plan:        # dropout descriptors of the recorded pass point at the device-resident seed
+                    blocks[k]()
             else:
                 blocks[k]()
             if last:

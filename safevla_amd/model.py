@@ -18,6 +18,7 @@ MI355X-first design (not a translation of the nn.Module graph):
     and shared by the three towers.
 No CPU / eager fallback: every op below is a C-ABI kernel (include/svla.h); missing library => import error.
 """
+import contextlib
 import math
 import os
 from typing import Dict, List, Optional, Tuple
@@ -40,8 +41,8 @@ TEXT_OFF = 1 + 2 * NPATCH
 MAX_ACTING_WINDOW = 1024          # keys of the single-query attention kernels = longest KV-cache window (max_steps) of the acting step
 TEXT_ENCODER_DIMS = {"t5-small": 512, "SigLIPBase": 768, "SigLIPLarge": 1024}
 BF16, F32 = torch.bfloat16, torch.float32
-import os as _os0
-_NO_COMPRESSOR_BITS = _os0.environ.get("SVLA_NO_COMPRESSOR_BITS", "0") == "1"     # A/B switch of the 1-bit compressor ReLU masks
+SEED_STEP = 0x3C6EF35             # what the device-resident dropout seed of a recorded / captured pass advances by per pass (Tower.advance_device_seed, svla_acting_stage)
+_NO_COMPRESSOR_BITS = os.environ.get("SVLA_NO_COMPRESSOR_BITS", "0") == "1"     # A/B switch of the 1-bit compressor ReLU masks
 
 
 class _NS(nn.Module):
@@ -59,6 +60,7 @@ class _Arena:
     def __init__(self):
         self.specs: List[Tuple[nn.Module, str, Tuple[int, ...], str]] = []
         self.offsets: Dict[int, Tuple[int, int]] = {}
+        self._tower_starts: List[int] = []
 
     def declare(self, owner: nn.Module, name: str, shape, init: str):
         self.specs.append((owner, name, tuple(shape), init))
@@ -70,12 +72,12 @@ class _Arena:
         pad = (-n) % align
         if pad:
             self.specs.append((None, "_pad", (pad,), "zeros"))
-        self._tower_starts = getattr(self, "_tower_starts", []) + [n + pad]
+        self._tower_starts.append(n + pad)
 
     def build(self, device):
         total = sum(int(np.prod(s[2])) for s in self.specs)
         total += (-total) % 256
-        starts = getattr(self, "_tower_starts", [0])
+        starts = self._tower_starts or [0]
         self.tower_ranges = [(a, b) for a, b in zip(starts, starts[1:] + [total])]
         self.total = total
         self.flat_p = torch.zeros(total, device=device, dtype=F32)
@@ -145,6 +147,7 @@ class Tower(nn.Module):
         # fp32 attention kernels through fp32 copies of the operands (ops.attn_fwd: a slow path)
         self.hdim, self.hdim_dec = d_model // n_heads, d_model // n_heads_decoder
         HD = self.dec_hidden = 256 * ((int(2 * 4 * d_model / 3) + 255) // 256)
+        F = self.dff = 2048               # feed-forward width of the fusion layers: nn.TransformerEncoderLayer's default, as the reference uses it
         self.dino_dim = dino_dim          # channel width of the frozen image features: 384 (ViT-S/14), 768 (ViT-B/14, SigLIP-B), 1024 (ViT-L), 2048 (CLIP RN50)
         # frozen text encoder and the width of its features (text_cond_visual_encoder.py:24-45 ``TEXT_ENCODER_DIMS`` / ``create_text_encoder``): the RL towers
         # and the t5 presets of the IL model use t5-small; the IL model's ``siglip_*`` presets the SigLIP text tower (tokens + pooled token, siglip_text.py)
@@ -168,10 +171,10 @@ class Tower(nn.Module):
             raise ValueError(f"max_steps = {max_steps}: the KV-cache window of the acting step is limited to {MAX_ACTING_WINDOW} steps")
         self.max_steps = max_steps
         self.time_step_counter = 0
-        self.prune_last = True      # dead-output elimination in the last fusion layer (exact; see run_forward)
-        # pruned last layer of an update pass: K / V projections absorbed into its single query, K and V never materialised (csrc/attn_q1.hip; run_forward).
+        self.prune_last = True      # dead-output elimination in the last fusion layer (exact; see _fusion_layer_fwd)
+        # pruned last layer of an update pass: K / V projections absorbed into its single query, K and V never materialised (csrc/attn_q1.hip; _fusion_layer_fwd).
         # SVLA_LAST_LAYER_KV=1 keeps the materialised K / V path (A/B)
-        self.absorb_last = _os0.environ.get("SVLA_LAST_LAYER_KV", "0") != "1"
+        self.absorb_last = os.environ.get("SVLA_LAST_LAYER_KV", "0") != "1"
         # BASELINE config 5 ("fp8 MFMA attention"): the full-sequence fusion-encoder attention layers run on the e4m3 / e5m2 kernels
         # (svla_attn_fp8_*); the pruned last layer (one query per row) and the decoder keep the bf16 kernels.  bf16 precision only.
         self.fp8_attention = False
@@ -181,6 +184,10 @@ class Tower(nn.Module):
         self.t5_dropout = True      # the frozen text encoder's own dropout (also active in the reference's train mode)
         self.drop_seed_base = 0x5AFE + 977 * len(arena.specs)   # distinct per tower; settable for reproducible tests
         self._fwd_count = 0
+        # acting path: llama KV caches (+ version: recorded steps hold pointers into them), eval-mode text-feature cache, gamma-folded decoder weights (refresh_folded), norm-fused
+        # GEMMs in the acting step's decoder / the frozen text encoder (None: by size).  Below: step counter, dropout seed, step indices of recorded / captured passes (device memory)
+        self._kv, self._kv_version, self._t5_cache, self._wg, self._wg_dirty, self.rms_fused, self.t5_fused = None, 0, (None, None), {}, True, True, None
+        self._t_dev = self._seed_dev = self._seed_dev_buf = self._ar_steps = self._last_full_logits = None
         dec = arena.declare
         ve = self.visual_encoder = _NS()
         dec(ve, "fusion_token", (D,), "tok")
@@ -203,8 +210,8 @@ class Tower(nn.Module):
             dec(l.self_attn, "in_proj_weight", (3 * D, D), "lin"); dec(l.self_attn, "in_proj_bias", (3 * D,), "zeros")
             l.self_attn.out_proj = _NS()
             dec(l.self_attn.out_proj, "weight", (D, D), "lin"); dec(l.self_attn.out_proj, "bias", (D,), "zeros")
-            l.linear1 = _NS(); dec(l.linear1, "weight", (2048, D), "lin"); dec(l.linear1, "bias", (2048,), "zeros")
-            l.linear2 = _NS(); dec(l.linear2, "weight", (D, 2048), "lin"); dec(l.linear2, "bias", (D,), "zeros")
+            l.linear1 = _NS(); dec(l.linear1, "weight", (F, D), "lin"); dec(l.linear1, "bias", (F,), "zeros")
+            l.linear2 = _NS(); dec(l.linear2, "weight", (D, F), "lin"); dec(l.linear2, "bias", (D,), "zeros")
             l.norm1 = _NS(); dec(l.norm1, "weight", (D,), "ones"); dec(l.norm1, "bias", (D,), "zeros")
             l.norm2 = _NS(); dec(l.norm2, "weight", (D,), "ones"); dec(l.norm2, "bias", (D,), "zeros")
             ve.fusion_xformer.layers.append(l)
@@ -262,7 +269,7 @@ class Tower(nn.Module):
                ("va", [ve.visual_adapter[0].weight], (D, D)), ("ta", [ve.text_adapter[0].weight], (D, self.text_dim))]
         for i, l in enumerate(ve.fusion_xformer.layers):
             out += [(f"f{i}.in", [l.self_attn.in_proj_weight], (3 * D, D)), (f"f{i}.out", [l.self_attn.out_proj.weight], (D, D)),
-                    (f"f{i}.l1", [l.linear1.weight], (2048, D)), (f"f{i}.l2", [l.linear2.weight], (D, 2048))]
+                    (f"f{i}.l1", [l.linear1.weight], (self.dff, D)), (f"f{i}.l2", [l.linear2.weight], (D, self.dff))]
         for i, l in enumerate(self.decoder.layers):
             a, f = l.attention, l.feed_forward
             out += [(f"d{i}.qkv", [a.wq.weight, a.wk.weight, a.wv.weight], (3 * D, D)), (f"d{i}.wo", [a.wo.weight], (D, D)),
@@ -297,11 +304,9 @@ class Tower(nn.Module):
         GEMMs (ops.gemm_nt_rmsa).  Persistent buffers refreshed IN PLACE (recorded acting steps hold their addresses), lazily: only an acting step after an
         optimiser step / load_state_dict pays for it."""
         D, H, HD = self.D, self.H, self.dec_hidden
-        if self.adt != BF16 or not getattr(self, "_wg_dirty", True):
+        if self.adt != BF16 or not self._wg_dirty:
             return
         ar = self.arena
-        if not hasattr(self, "_wg"):
-            self._wg = {}
         for i, l in enumerate(self.decoder.layers):
             a, f = l.attention, l.feed_forward
             for key, first, n, gamma in ((f"d{i}.qkv", a.wq.weight, 3 * D, l.attention_norm.weight), (f"d{i}.w13", f.w1.weight, 2 * HD, l.ffn_norm.weight)):
@@ -324,177 +329,209 @@ class Tower(nn.Module):
 
     def _site_fn(self, seed):
         p = self.dropout_p
-        sd = getattr(self, "_seed_dev", None)      # captured acting graph: the pass seed lives in device memory (fresh noise per replay)
+        sd = self._seed_dev      # captured acting graph: the pass seed lives in device memory (fresh noise per replay)
         return (lambda i, k, rm=1: ops.Dropout(seed, 4 * i + k, p, rm, seed_dev=sd)) if seed is not None else (lambda i, k, rm=1: None)
 
     def g(self, p):  # fp32 grad view of a parameter
         return self.arena.slab(p, self.arena.flat_g)
 
-    # ---- forward ----------------------------------------------------------------------------------------------
     # ---- acting path state (llama KV caches, llama/model.py:224-247; counter semantics allenact_dino_transformer.py:376-406)
     def _ensure_caches(self, B: int):
-        D, H, HD = self.D, self.H, self.dec_hidden
-        if getattr(self, "_kv", None) is None or self._kv[0].shape[0] < B:
-            self._kv_version = getattr(self, "_kv_version", 0) + 1        # recorded steps hold pointers into the caches: new caches, new plans
-            self._kv = [torch.zeros(B, self.max_steps, 2 * D, device=self.device_, dtype=self.adt) for _ in self.decoder.layers]
+        if self._kv is None or self._kv[0].shape[0] < B:
+            self._kv_version += 1        # recorded steps hold pointers into the caches: new caches, new plans
+            self._kv = [torch.zeros(B, self.max_steps, 2 * self.D, device=self.device_, dtype=self.adt) for _ in self.decoder.layers]
 
     def cache_select(self, keep: list):
-        if getattr(self, "_kv", None) is not None:
+        if self._kv is not None:
             idx = torch.as_tensor(keep, device=self.device_, dtype=torch.long)
             self._kv = [c[idx].contiguous() for c in self._kv]
-            self._kv_version = getattr(self, "_kv_version", 0) + 1
+            self._kv_version += 1
 
+    # ---- dropout seed of recorded / captured passes: in device memory, read when a kernel starts, so every replay draws fresh noise
+    def advance_device_seed(self):
+        """once before every recorded, captured or replayed pass (its forward and backward read the same seed); wraps in int32"""
+        if self._seed_dev_buf is None:      # created on first use
+            self._seed_dev_buf = torch.tensor([(self.drop_seed_base * 0x9E3779B1) & 0x7FFFFFFF], device=self.device_, dtype=torch.int32)
+        self._seed_dev_buf.add_(SEED_STEP)
+
+    @contextlib.contextmanager
+    def device_resident(self, t_dev=None):
+        """Inside, no kernel argument depends on the step (recording, capture): dropout descriptors point at the device seed, acting steps read the counter ``t_dev``."""
+        self._t_dev, self._seed_dev = t_dev, self._seed_dev_buf
+        try:
+            yield
+        finally:
+            self._t_dev = self._seed_dev = None
+
+    def static_step(self, st: "_ActingState"):
+        """One acting forward on the static buffers of ``st`` in the step-independent form -> (logits, values); the wrapper advances the host counter once per step."""
+        keep = self.time_step_counter
+        with self.device_resident(st.t_dev):
+            logits, values, _ = self.run_forward(st, need_grad=False)
+        self.time_step_counter = keep
+        return logits, values
+
+    # ---- forward: a driver over one method per stage ---------------------------------------------------------------------------
     def run_forward(self, prep: "Prep", need_grad: bool):
-        D, H, HD = self.D, self.H, self.dec_hidden
-        SCF, SCD = self.hdim ** -0.5, self.hdim_dec ** -0.5          # 0.125 for 64-wide heads
-        T, B, R, S, L, U = prep.T, prep.B, prep.R, prep.S, prep.L, prep.U
-        if T > 1 or need_grad or not getattr(prep, "acting", True) or self.time_step_counter >= self.max_steps:
+        """-> logits [T, B, A], values [T, B, 1], the saved activations for ``run_backward`` (opaque to callers; None without ``need_grad``)"""
+        D, T, B, S = self.D, prep.T, prep.B, prep.S
+        if T > 1 or need_grad or not prep.acting or self.time_step_counter >= self.max_steps:
             self.time_step_counter = 0
-        ve, w = self.visual_encoder, self._w
-        M2, M = R * 2 * NPATCH, R * S
-        c = {}  # saved activations
-        c["drop_seed"], site = self._drop_sites()
+        seed, site = self._drop_sites()
+        c = dict(drop_seed=seed, fusion=[])  # saved activations
+        xf = self._inputs_fwd(prep, c, need_grad)
+        nfl = len(self.visual_encoder.fusion_xformer.layers)
+        for i in range(nfl):
+            xf, saved = self._fusion_layer_fwd(i, xf, prep, site, need_grad)
+            if need_grad:
+                c["fusion"].append(saved)
+        # decoder over the rollout time axis, rows (b*T + t); a pruned last fusion layer left the position-0 rows only
+        xd = torch.empty(prep.R, D, device=self.device_, dtype=self.adt)
+        ops.decoder_embed_fwd(xf, D if nfl and self.prune_last else S * D, self.last_actions_embed.weight, self.object_in_hand_embed.weight,
+                              self.time_encoder.div_term, prep.prev_actions, prep.masks, prep.hand, prep.time_step, T, B, xd)
+        if T == 1 and not need_grad and prep.acting:
+            # acting: one new token per env against the KV cache.  A one-step UPDATE batch (need_grad) takes the sequence form -- a sequence of length one has no
+            # history to attend to, and the backward needs the saved activations -- and so does a batch whose Prep says ``acting = False`` (the imitation-learning
+            # model's ``forward(batch)`` on one-step windows: independent sequences, never the cache of an earlier call; its online agent sets ``acting = True``)
+            xd, c["dec"] = self._decoder_step_fwd(xd, prep), []
+        else:
+            xd, c["dec"] = self._decoder_seq_fwd(xd, prep, need_grad)
+        logits, values = self._heads_fwd(xd, prep, c, need_grad)
+        c["xf_last"] = xf
+        return logits.view(T, B, N_ACTIONS), values.view(T, B, 1), (c if need_grad else None)
+
+    def _inputs_fwd(self, prep, c, need_grad):
+        """Visual compressor + adapter (both cameras), frozen text encoder + text adapter, ``fusion_fill`` -> the fusion transformer's input rows [R * S, D]"""
+        D, R, S, L, U, ve, w = self.D, prep.R, prep.S, prep.L, prep.U, self.visual_encoder, self._w
+        M2 = R * 2 * NPATCH
         tok = prep.tokens.view(M2, self.dino_dim)
         # ReLU derivatives of the two compressor convs as 1 bit per element (like the feed-forward's): the input-gradient GEMMs then read
         # M2 x 64 mask bytes instead of re-reading a whole M2 x 512 bf16 activation
         bits = need_grad and self.adt == BF16 and not _NO_COMPRESSOR_BITS
-        c1b = torch.empty(ops.relu_bits_bytes(M2, D), device=self.device_, dtype=torch.uint8) if bits else None
-        c2b = torch.empty(ops.relu_bits_bytes(M2, D), device=self.device_, dtype=torch.uint8) if bits else None
+        c1b, c2b = (torch.empty(ops.relu_bits_bytes(M2, D), device=self.device_, dtype=torch.uint8) if bits else None for _ in range(2))
         c1 = ops.gemm_nt(tok, w["c1"], M2, D, self.dino_dim, bias=ve.visual_compressor[0].bias, act=ops.ACT_RELU, relu_bits_out=c1b)
         c2 = ops.gemm_nt(c1, w["c2"], M2, D, D, bias=ve.visual_compressor[2].bias, act=ops.ACT_RELU, relu_bits_out=c2b)
         a1 = ops.gemm_nt(c2, w["va"], M2, D, D, bias=ve.visual_adapter[0].bias)
         x = torch.empty(R, S, D, device=self.device_, dtype=self.adt)
         _, va_mean, va_rstd = ops.norm_fwd(a1, ve.visual_adapter[1].weight, ve.visual_adapter[1].bias, 1e-5, M2, relu=True,
                                            tok=self._camtok, tok_group=NPATCH, y=x, ymap=(2 * NPATCH, S, 1), D=D)
-        t5_seed = c["drop_seed"] if self.t5_dropout else None
-        key = getattr(prep, "ids_key", None)
-        if t5_seed is None and key is not None and getattr(self, "_t5_cache", (None, None))[0] == key:
+        t5_seed, key = (c["drop_seed"] if self.t5_dropout else None), prep.ids_key
+        if t5_seed is None and key is not None and self._t5_cache[0] == key:
             t5 = self._t5_cache[1]     # eval mode: the frozen encoder is a pure function of the goal tokens (one episode = one goal)
         else:
-            t5 = ve.text_encoder.encode(prep.ids, getattr(prep, "attn_mask_u8", None) if getattr(prep, "attn_mask_u8", None) is not None else prep.attn_mask,
-                                        drop_seed=t5_seed, drop_p=self.dropout_p, dtype=self.adt,
-                                        seed_dev=getattr(self, "_seed_dev", None), fused=getattr(self, "t5_fused", None))   # [U*L, text_dim], frozen (SigLIP: ids are [U, L - 1], the pooled token is row L - 1)
+            t5 = ve.text_encoder.encode(prep.ids, prep.attn_mask_u8 if prep.attn_mask_u8 is not None else prep.attn_mask, drop_seed=t5_seed, drop_p=self.dropout_p,
+                                        dtype=self.adt, seed_dev=self._seed_dev, fused=self.t5_fused)   # [U*L, text_dim], frozen (SigLIP: ids are [U, L - 1], the pooled token is row L - 1)
             self._t5_cache = (key, t5) if (t5_seed is None and key is not None) else (None, None)
         ta = ops.gemm_nt(t5, w["ta"], U * L, D, self.text_dim, bias=ve.text_adapter[0].bias)
         tf, ta_mean, ta_rstd = ops.norm_fwd(ta, ve.text_adapter[1].weight, ve.text_adapter[1].bias, 1e-5, U * L, relu=True, D=D)
         ops.fusion_fill(ve.fusion_token, tf, prep.gid, x, R, S, L, TEXT_OFF)
         c.update(c1=c1, c2=c2, c1b=c1b, c2b=c2b, a1=a1, va=(va_mean, va_rstd), t5=t5, ta=ta, ta_stats=(ta_mean, ta_rstd))
-        xf = x.view(M, D)
-        fl = []
-        nfl = len(ve.fusion_xformer.layers)
-        xf_stride = S * D
-        for i, l in enumerate(ve.fusion_xformer.layers):
-            if i == nfl - 1 and self.prune_last:
-                # Only sequence position 0 of the last fusion layer is consumed (allenact_dino_transformer.py:708 x[:, 0]):
-                # Q / attention / out_proj / norm1 / FFN / norm2 run on the R position-0 rows only; K/V still cover all tokens (projected in full, or
-                # absorbed into the query: below).  Identical outputs and gradients; ~84 % less work in this layer.
-                b_in = l.self_attn.in_proj_bias
-                q0 = ops.gemm_nt(xf, w[f"f{i}.in"][:D], R, D, D, bias=b_in[:D], lda=S * D)
-                # Update passes on the bf16 path: with one query per (row, head) the K and V projections move onto the query side exactly --
-                # qt_h = W_k,h^T q_h scores the raw tokens (the K bias shifts every score of a head alike: the softmax drops it), c_h = sum_j pd_hj x_j,
-                # o_h = W_v,h c_h + (sum_j pd_hj) b_v,h -- so K / V for all M tokens are never computed or kept.  The per-head products are plain GEMMs over
-                # head-expanded [8 R, 512] rows.  Acting steps, fp32 verification mode and absorb_last = False take the materialised branch below.
-                absorbed = need_grad and self.absorb_last and self.adt == BF16 and self.hdim == 64 and H == 8 and S <= 256
-                if absorbed:
-                    eq, _, _ = ops.head_expand(q0, R)
-                    qt = ops.gemm_nt(eq, self._wt[f"f{i}.in"][:, D:2 * D], 8 * R, D, D)
-                    cc, sig, prob = ops.attn_q1_fwd(xf, S * D, qt, R, S, SCF, drop=site(i, 0))
-                    ao = ops.head_pick(ops.gemm_nt(cc, w[f"f{i}.in"][2 * D:], 8 * R, D, D), R, sigma=sig, bias=b_in[2 * D:])
-                    att = dict(absorbed=True, eq=eq, qt=qt, cc=cc, sig=sig, prob=prob)
-                else:
-                    kv = ops.gemm_nt(xf, w[f"f{i}.in"][D:], M, 2 * D, D, bias=b_in[D:])
-                    ao, lse = ops.attn_fwd(q0, kv, kv[:, D:], 2 * D, R, S, H, SCF, save_lse=need_grad, Sq=1, ldq=D, drop=site(i, 0), head_dim=self.hdim)
-                    att = dict(absorbed=False, kv=kv, lse=lse)
-                h1 = ops.gemm_nt(ao, w[f"f{i}.out"], R, D, D, bias=l.self_attn.out_proj.bias, residual=xf, ldr=S * D, drop=site(i, 1, S))
-                x1, m1, r1 = ops.norm_fwd(h1, l.norm1.weight, l.norm1.bias, 1e-5, R, save_stats=need_grad, D=D)
-                f1 = ops.gemm_nt(x1, w[f"f{i}.l1"], R, 2048, D, bias=l.linear1.bias, act=ops.ACT_RELU, drop=site(i, 2, S))
-                h2 = ops.gemm_nt(f1, w[f"f{i}.l2"], R, D, 2048, bias=l.linear2.bias, residual=x1, drop=site(i, 3, S))
-                xo, m2, r2 = ops.norm_fwd(h2, l.norm2.weight, l.norm2.bias, 1e-5, R, save_stats=need_grad, D=D)
-                if need_grad:
-                    fl.append(dict(pruned=True, x=xf, q0=q0, ao=ao, **att, h1=h1, x1=x1, n1=(m1, r1), f1=f1, h2=h2, n2=(m2, r2)))
-                xf, xf_stride = xo, D
-                continue
-            qkv = ops.gemm_nt(xf, w[f"f{i}.in"], M, 3 * D, D, bias=l.self_attn.in_proj_bias)
-            f8 = None
-            if self.fp8_attention and self.adt == BF16 and S <= 256 and self.hdim == 64:
-                f8 = ops.attn_fp8_quant(qkv, 3 * D, R, S, H)
-                ao, lse = ops.attn_fp8_fwd(f8, SCF, save_lse=need_grad, drop=site(i, 0))
-                qkv = None                       # the backward reads the e4m3 copies
+        return x.view(R * S, D)
+
+    def _fusion_layer_fwd(self, i, xf, prep, site, need_grad):
+        """Fusion layer ``i`` on the token rows ``xf`` [R * S, D] -> (output rows, saved activations or None).  Its attention half has four forms (absorbed single
+        query, single query over materialised K / V, fp8, full QKV) that meet at ``ao``; the rest of the layer is ``_fusion_post_fwd``."""
+        D, H, R, S, w, SCF = self.D, self.H, prep.R, prep.S, self._w, self.hdim ** -0.5          # SCF: 0.125 for 64-wide heads
+        M, l = R * S, self.visual_encoder.fusion_xformer.layers[i]
+        if self.prune_last and i == len(self.visual_encoder.fusion_xformer.layers) - 1:
+            # Only sequence position 0 of the last fusion layer is consumed (allenact_dino_transformer.py:708 x[:, 0]): Q / attention / out_proj / norm1 / FFN /
+            # norm2 run on the R position-0 rows only; K/V still cover all tokens (projected in full, or absorbed into the query: below).  Identical outputs and
+            # gradients; ~84 % less work in this layer.
+            b_in = l.self_attn.in_proj_bias
+            q0 = ops.gemm_nt(xf, w[f"f{i}.in"][:D], R, D, D, bias=b_in[:D], lda=S * D)
+            # Update passes on the bf16 path: with one query per (row, head) the K and V projections move onto the query side exactly --
+            # qt_h = W_k,h^T q_h scores the raw tokens (the K bias shifts every score of a head alike: the softmax drops it), c_h = sum_j pd_hj x_j,
+            # o_h = W_v,h c_h + (sum_j pd_hj) b_v,h -- so K / V for all M tokens are never computed or kept.  The per-head products are plain GEMMs over
+            # head-expanded [8 R, 512] rows.  Acting steps, fp32 verification mode and absorb_last = False take the materialised branch below.
+            if need_grad and self.absorb_last and self.adt == BF16 and self.hdim == 64 and H == 8 and S <= 256:
+                eq, _, _ = ops.head_expand(q0, R)
+                qt = ops.gemm_nt(eq, self._wt[f"f{i}.in"][:, D:2 * D], 8 * R, D, D)
+                cc, sig, prob = ops.attn_q1_fwd(xf, S * D, qt, R, S, SCF, drop=site(i, 0))
+                ao = ops.head_pick(ops.gemm_nt(cc, w[f"f{i}.in"][2 * D:], 8 * R, D, D), R, sigma=sig, bias=b_in[2 * D:])
+                att = dict(absorbed=True, eq=eq, qt=qt, cc=cc, sig=sig, prob=prob)
             else:
-                ao, lse = ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, R, S, H, SCF, save_lse=need_grad, drop=site(i, 0), head_dim=self.hdim)
-            h1 = ops.gemm_nt(ao, w[f"f{i}.out"], M, D, D, bias=l.self_attn.out_proj.bias, residual=xf, drop=site(i, 1))
-            x1, m1, r1 = ops.norm_fwd(h1, l.norm1.weight, l.norm1.bias, 1e-5, M, save_stats=need_grad, D=D)
-            # the ReLU derivative is kept as 1 bit per element (M x 256 bytes): the input-gradient GEMM then reads 16x fewer mask bytes
-            f1b = torch.empty(ops.relu_bits_bytes(M, 2048), device=x1.device, dtype=torch.uint8) if (need_grad and self.adt == BF16) else None
-            f1 = ops.gemm_nt(x1, w[f"f{i}.l1"], M, 2048, D, bias=l.linear1.bias, act=ops.ACT_RELU, relu_bits_out=f1b, drop=site(i, 2))
-            h2 = ops.gemm_nt(f1, w[f"f{i}.l2"], M, D, 2048, bias=l.linear2.bias, residual=x1, drop=site(i, 3))
-            xo, m2, r2 = ops.norm_fwd(h2, l.norm2.weight, l.norm2.bias, 1e-5, M, save_stats=need_grad, D=D)
-            if need_grad:
-                fl.append(dict(pruned=False, x=xf, qkv=qkv, f8=f8, ao=ao, lse=lse, h1=h1, x1=x1, n1=(m1, r1), f1=f1, f1b=f1b, h2=h2, n2=(m2, r2)))
-            xf = xo
-        c["fusion"] = fl
-        # decoder over the rollout time axis, rows (b*T + t)
-        j = torch.empty(R, D, device=self.device_, dtype=self.adt)
-        ops.decoder_embed_fwd(xf, xf_stride, self.last_actions_embed.weight, self.object_in_hand_embed.weight,
-                              self.time_encoder.div_term, prep.prev_actions, prep.masks, prep.hand, prep.time_step, T, B, j)
-        xd = j
-        dl = []
-        if T == 1 and not need_grad and getattr(prep, "acting", True):
-            # acting: one new token per env against the KV cache; env b attends to cache slots >= max(counter - time_step_b, 0)
-            # (its current episode), allenact_dino_transformer.py:388-397.  A one-step UPDATE batch (need_grad: engine / fused-loss path on a T = 1 rollout)
-            # takes the sequence branch below instead -- a sequence of length one has no history to attend to, and the backward needs the saved activations --
-            # and so does a batch whose Prep says ``acting = False`` (the imitation-learning model's ``forward(batch)`` on one-step windows: independent
-            # sequences, never the cache of an earlier call; its online agent sets ``acting = True``)
-            if self.hdim_dec != 64:
-                raise NotImplementedError("KV-cached single steps need 64-wide decoder heads (MFMA / decode attention kernels)")
-            t = self.time_step_counter
-            self._ensure_caches(B)
-            t_dev = getattr(self, "_t_dev", None)
-            if t_dev is None:
-                start = torch.clamp(t - prep.time_step, min=0)
-                kvalid = (torch.arange(t + 1, device=self.device_)[None, :] >= start[:, None]).to(torch.uint8).contiguous()
-                S_att = t + 1
-            else:
-                # captured / recorded form: the step counter lives in device memory, so every kernel argument is step-independent --
-                # attention runs over the whole cache window and the mask hides the slots beyond the counter
-                kvalid = getattr(prep, "kvalid_static", None)        # shared by the three towers (a function of the step and time_step only)
-                if kvalid is None:
-                    ar = self._ar_steps
-                    kvalid = ((ar[None, :] <= t_dev) & (ar[None, :] >= torch.clamp(t_dev - prep.time_step, min=0)[:, None])).to(torch.uint8).contiguous()
-                S_att = self.max_steps
-            # bf16 product path: RMSNorm folded into the following GEMM (one launch instead of two).  The update's sequence branch runs norm -> bf16 -> GEMM (its backward
-            # needs the normed activation), so a rollout's old log-probs and the update's recomputed ones differ by that one rounding of the decoder's normed rows --
-            # bounded by tests/test_model_gpu.py::test_fused_rmsnorm_step_close_to_unfused; ``rms_fused = False`` runs the acting step on the two-launch form
-            fused = self.adt == BF16 and getattr(self, "rms_fused", True)
-            if fused:
-                self.refresh_folded()
-            for i, l in enumerate(self.decoder.layers):
-                if fused:
-                    qkv = ops.gemm_nt_rmsa(xd, self._wg[f"d{i}.qkv"], B, 3 * D, D, 1e-5)
-                else:
-                    n1, _, _ = ops.norm_fwd(xd, l.attention_norm.weight, None, 1e-5, B, rms=True, save_stats=False, D=D)
-                    qkv = ops.gemm_nt(n1, w[f"d{i}.qkv"], B, 3 * D, D)
-                cache = self._kv[i]
-                if t_dev is None:
-                    cache[:B, t].copy_(qkv[:, D:])
-                elif self.adt == BF16:
-                    ops.kv_append(qkv[:, D:], 3 * D, cache, t_dev, B, 2 * D)
-                else:
-                    cache[:B].index_copy_(1, t_dev.view(1), qkv[:, D:].unsqueeze(1))
-                cv = cache.view(-1, 2 * D)
-                ao, _ = ops.attn_fwd(qkv, cv, cv[:, D:], 2 * D, B, S_att, self.Hdec, SCD, kvalid=kvalid, save_lse=False, Sq=1, ldq=3 * D,
-                                     kv_rows=self.max_steps)
-                h = ops.gemm_nt(ao, w[f"d{i}.wo"], B, D, D, residual=xd)
-                if fused:
-                    ab = ops.gemm_nt_rmsa(h, self._wg[f"d{i}.w13"], B, 2 * HD, D, 1e-5)
-                else:
-                    n2, _, _ = ops.norm_fwd(h, l.ffn_norm.weight, None, 1e-5, B, rms=True, save_stats=False, D=D)
-                    ab = ops.gemm_nt(n2, w[f"d{i}.w13"], B, 2 * HD, D)
-                gg = ops.swiglu_fwd(ab, B, HD)
-                xd = ops.gemm_nt(gg, w[f"d{i}.w2"], B, D, HD, residual=h)
-            self.time_step_counter += 1
+                kv = ops.gemm_nt(xf, w[f"f{i}.in"][D:], M, 2 * D, D, bias=b_in[D:])
+                ao, lse = ops.attn_fwd(q0, kv, kv[:, D:], 2 * D, R, S, H, SCF, save_lse=need_grad, Sq=1, ldq=D, drop=site(i, 0), head_dim=self.hdim)
+                att = dict(absorbed=False, kv=kv, lse=lse)
+            xo, post = self._fusion_post_fwd(i, ao, R, xf, S * D, S, False, site, need_grad)
+            return xo, (dict(pruned=True, x=xf, q0=q0, ao=ao, **att, **post) if need_grad else None)
+        qkv = ops.gemm_nt(xf, w[f"f{i}.in"], M, 3 * D, D, bias=l.self_attn.in_proj_bias)
+        f8 = None
+        if self.fp8_attention and self.adt == BF16 and S <= 256 and self.hdim == 64:
+            f8 = ops.attn_fp8_quant(qkv, 3 * D, R, S, H)
+            ao, lse = ops.attn_fp8_fwd(f8, SCF, save_lse=need_grad, drop=site(i, 0))
+            qkv = None                       # the backward reads the e4m3 copies
         else:
-          for i, l in enumerate(self.decoder.layers):
+            ao, lse = ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, R, S, H, SCF, save_lse=need_grad, drop=site(i, 0), head_dim=self.hdim)
+        xo, post = self._fusion_post_fwd(i, ao, M, xf, None, 1, need_grad and self.adt == BF16, site, need_grad)
+        return xo, (dict(pruned=False, x=xf, qkv=qkv, f8=f8, ao=ao, lse=lse, **post) if need_grad else None)
+
+    def _fusion_post_fwd(self, i, ao, rows, residual, ldr, row_mult, bits, site, need_grad):
+        """Post-attention half of fusion layer ``i`` on ``rows`` rows: out_proj (+ residual, dropout) -> norm1 -> linear1 (ReLU, dropout) -> linear2 (+ residual, dropout) -> norm2.
+        ``ldr``: leading dimension of ``residual`` (position-0 rows of all tokens: S * D); ``row_mult``: row step of the dropout counters; ``bits``: keep linear1's ReLU derivative as bits"""
+        D, F, w, l = self.D, self.dff, self._w, self.visual_encoder.fusion_xformer.layers[i]
+        h1 = ops.gemm_nt(ao, w[f"f{i}.out"], rows, D, D, bias=l.self_attn.out_proj.bias, residual=residual, ldr=ldr, drop=site(i, 1, row_mult))
+        x1, m1, r1 = ops.norm_fwd(h1, l.norm1.weight, l.norm1.bias, 1e-5, rows, save_stats=need_grad, D=D)
+        f1b = torch.empty(ops.relu_bits_bytes(rows, F), device=x1.device, dtype=torch.uint8) if bits else None
+        f1 = ops.gemm_nt(x1, w[f"f{i}.l1"], rows, F, D, bias=l.linear1.bias, act=ops.ACT_RELU, relu_bits_out=f1b, drop=site(i, 2, row_mult))
+        h2 = ops.gemm_nt(f1, w[f"f{i}.l2"], rows, D, F, bias=l.linear2.bias, residual=x1, drop=site(i, 3, row_mult))
+        xo, m2, r2 = ops.norm_fwd(h2, l.norm2.weight, l.norm2.bias, 1e-5, rows, save_stats=need_grad, D=D)
+        return xo, dict(h1=h1, x1=x1, n1=(m1, r1), f1=f1, f1b=f1b, h2=h2, n2=(m2, r2))
+
+    def _decoder_step_fwd(self, xd, prep):
+        """The llama decoder as one KV-cached step: env b attends to cache slots >= max(counter - time_step_b, 0), its current episode (allenact_dino_transformer.py:388-397)"""
+        D, HD, B, w, SCD = self.D, self.dec_hidden, prep.B, self._w, self.hdim_dec ** -0.5
+        if self.hdim_dec != 64:
+            raise NotImplementedError("KV-cached single steps need 64-wide decoder heads (MFMA / decode attention kernels)")
+        t, t_dev = self.time_step_counter, self._t_dev
+        self._ensure_caches(B)
+        if t_dev is None:
+            start = torch.clamp(t - prep.time_step, min=0)
+            kvalid = (torch.arange(t + 1, device=self.device_)[None, :] >= start[:, None]).to(torch.uint8).contiguous()
+            S_att = t + 1
+        else:
+            # captured / recorded form: the step counter lives in device memory, so every kernel argument is step-independent --
+            # attention runs over the whole cache window and the mask hides the slots beyond the counter
+            kvalid = prep.kvalid_static        # shared by the three towers (a function of the step and time_step only)
+            if kvalid is None:
+                ar = self._ar_steps
+                kvalid = ((ar[None, :] <= t_dev) & (ar[None, :] >= torch.clamp(t_dev - prep.time_step, min=0)[:, None])).to(torch.uint8).contiguous()
+            S_att = self.max_steps
+        # bf16 product path: RMSNorm folded into the following GEMM (one launch instead of two).  The update's sequence form runs norm -> bf16 -> GEMM (its backward
+        # needs the normed activation), so a rollout's old log-probs and the update's recomputed ones differ by that one rounding of the decoder's normed rows --
+        # bounded by tests/test_model_gpu.py::test_fused_rmsnorm_step_close_to_unfused; ``rms_fused = False`` runs the acting step on the two-launch form
+        fused = self.adt == BF16 and self.rms_fused
+        if fused:
+            self.refresh_folded()
+
+        def normed_gemm(x, norm, key, n):
+            if fused:
+                return ops.gemm_nt_rmsa(x, self._wg[key], B, n, D, 1e-5)
+            y, _, _ = ops.norm_fwd(x, norm.weight, None, 1e-5, B, rms=True, save_stats=False, D=D)
+            return ops.gemm_nt(y, w[key], B, n, D)
+        for i, l in enumerate(self.decoder.layers):
+            qkv = normed_gemm(xd, l.attention_norm, f"d{i}.qkv", 3 * D)
+            cache = self._kv[i]
+            if t_dev is None:
+                cache[:B, t].copy_(qkv[:, D:])
+            elif self.adt == BF16:
+                ops.kv_append(qkv[:, D:], 3 * D, cache, t_dev, B, 2 * D)
+            else:
+                cache[:B].index_copy_(1, t_dev.view(1), qkv[:, D:].unsqueeze(1))
+            cv = cache.view(-1, 2 * D)
+            ao, _ = ops.attn_fwd(qkv, cv, cv[:, D:], 2 * D, B, S_att, self.Hdec, SCD, kvalid=kvalid, save_lse=False, Sq=1, ldq=3 * D,
+                                 kv_rows=self.max_steps)
+            h = ops.gemm_nt(ao, w[f"d{i}.wo"], B, D, D, residual=xd)
+            gg = ops.swiglu_fwd(normed_gemm(h, l.ffn_norm, f"d{i}.w13", 2 * HD), B, HD)
+            xd = ops.gemm_nt(gg, w[f"d{i}.w2"], B, D, HD, residual=h)
+        self.time_step_counter += 1
+        return xd
+
+    def _decoder_seq_fwd(self, xd, prep, need_grad):
+        """The llama decoder over whole sequences, rows (b*T + t), causal within a trajectory -> (output rows, saved activations per layer)"""
+        D, HD, T, B, R, w, SCD = self.D, self.dec_hidden, prep.T, prep.B, prep.R, self._w, self.hdim_dec ** -0.5
+        dl = []
+        for i, l in enumerate(self.decoder.layers):
             n1, _, r1 = ops.norm_fwd(xd, l.attention_norm.weight, None, 1e-5, R, rms=True, save_stats=need_grad, D=D)
             qkv = ops.gemm_nt(n1, w[f"d{i}.qkv"], R, 3 * D, D)
             ao, lse = ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, B, T, self.Hdec, SCD, head_dim=self.hdim_dec, mask_mode=ops.MASK_BLOCK_CAUSAL,
@@ -507,17 +544,21 @@ class Tower(nn.Module):
             if need_grad:
                 dl.append(dict(x=xd, n1=n1, r1=r1, qkv=qkv, ao=ao, lse=lse, h=h, n2=n2, r2=r2, ab=ab, g=gg))
             xd = xo
+        return xd, dl
+
+    def _heads_fwd(self, xd, prep, c, need_grad):
+        """final RMSNorm + output projection -> beliefs (fp32, rows b*T + t) -> actor logits and critic values (rows t*B + b)"""
+        D, T, B, R = self.D, prep.T, prep.B, prep.R
         nf, _, rf = ops.norm_fwd(xd, self.decoder.norm.weight, None, 1e-5, R, rms=True, save_stats=need_grad, D=D)
-        beliefs = ops.gemm_nt(nf, w["dout"], R, D, D, out_f32=True)             # fp32, rows (b*T + t)
-        logits = ops.small_linear_fwd(beliefs, self.actor.linear.weight, self.actor.linear.bias, T, B)   # rows (t*B + b)
-        full_logits = None
+        beliefs = ops.gemm_nt(nf, self._w["dout"], R, D, D, out_f32=True)
+        logits = ops.small_linear_fwd(beliefs, self.actor.linear.weight, self.actor.linear.bias, T, B)
+        self._last_full_logits = None        # [T, B, 101] fp32 (critic_type == "discrete"), read by the 3-tower wrapper / engine
         if self.critic_type == "linear":
             values = ops.small_linear_fwd(beliefs, self.critic.fc.weight, self.critic.fc.bias, T, B)
         else:
-            values, full_logits, c["head"] = self._critic_head_fwd(beliefs, T, B)
-        c.update(dec=dl, xd_last=xd, nf=nf, rf=rf, beliefs=beliefs, xf_last=xf)
-        self._last_full_logits = full_logits        # [T, B, 101] fp32 (critic_type == "discrete"), read by the 3-tower wrapper / engine
-        return logits.view(T, B, N_ACTIONS), values.view(T, B, 1), (c if need_grad else None)
+            values, self._last_full_logits, c["head"] = self._critic_head_fwd(beliefs, T, B)
+        c.update(xd_last=xd, nf=nf, rf=rf, beliefs=beliefs)
+        return logits, values
 
     # ---- MLP / discrete critic heads (fp32, strided-GEMM kernel; rows come in decoder order b*T + t, leave in (t*B + b)) --------
     def _critic_head_fwd(self, beliefs, T, B):
@@ -557,38 +598,51 @@ class Tower(nn.Module):
             else:
                 dy = ops.gemm_f32(dy, w, R, n_in, n_out, sb=(1, n_in), mask=x)                              # ... through the ReLU
 
-    # ---- backward -----------------------------------------------------------------------------------------------
+    # ---- backward: the same stages in reverse ----------------------------------------------------------------------------------
     def run_backward(self, prep: "Prep", c, dlogits: Optional[torch.Tensor], dvalues: Optional[torch.Tensor],
                      dfull_logits: Optional[torch.Tensor] = None):
         """Accumulates parameter gradients into the arena's flat grad buffer.  ``dfull_logits``: gradient of the discrete critic's
         bin logits (HL-Gauss loss), critic_type == "discrete" only."""
-        D, H, HD = self.D, self.H, self.dec_hidden
-        SCF, SCD = self.hdim ** -0.5, self.hdim_dec ** -0.5          # 0.125 for 64-wide heads
-        T, B, R, S, L, U = prep.T, prep.B, prep.R, prep.S, prep.L, prep.U
-        ve, w, wt, dw, g = self.visual_encoder, self._w, self._wt, self._dw, self.g
-        M2, M = R * 2 * NPATCH, R * S
-        dev = self.device_
-        dbel = torch.empty(R, D, device=dev, dtype=F32)
-        first = True
-        if dlogits is not None:
-            ops.small_linear_bwd(c["beliefs"], self.actor.linear.weight, dlogits.reshape(R, N_ACTIONS).contiguous(), dbel,
-                                 g(self.actor.linear.weight), g(self.actor.linear.bias), T, B, accumulate_dx=False)
-            first = False
-        if self.critic_type != "linear":
-            if dvalues is not None or dfull_logits is not None:
-                self._critic_head_bwd(c["head"], T, B, dvalues, dfull_logits, dbel, accumulate_dx=not first)
-                first = False
-        elif dvalues is not None:
-            ops.small_linear_bwd(c["beliefs"], self.critic.fc.weight, dvalues.reshape(R, 1).contiguous(), dbel,
-                                 g(self.critic.fc.weight), g(self.critic.fc.bias), T, B, accumulate_dx=not first)
-            first = False
-        if first:
+        D, T, B, R, S, g = self.D, prep.T, prep.B, prep.R, prep.S, self.g
+        dx = self._heads_bwd(prep, c, dlogits, dvalues, dfull_logits)
+        if dx is None:
             return
-        dy = torch.empty(R, D, device=dev, dtype=self.adt)
+        dx = self._decoder_seq_bwd(prep, c, dx)
+        # gradient of the fusion transformer's output: the position-0 rows only behind a pruned last layer, else all token rows (zero but for position 0)
+        pruned = bool(c["fusion"]) and c["fusion"][-1]["pruned"]
+        dyf = torch.empty(R, D, device=self.device_, dtype=self.adt) if pruned else ops.zeros(R, S, D, device=self.device_, dtype=self.adt).view(R * S, D)
+        ops.decoder_embed_bwd(dx, prep.prev_actions, prep.masks, prep.hand, T, B, dyf, D if pruned else S * D, g(self.last_actions_embed.weight),
+                              g(self.object_in_hand_embed.weight))
+        site = self._site_fn(c.get("drop_seed"))
+        drop_scale = 1.0 / (1.0 - self.dropout_p) if c.get("drop_seed") is not None else 1.0
+        for i in reversed(range(len(c["fusion"]))):
+            dyf = self._fusion_layer_bwd(i, c["fusion"][i], dyf, prep, site, drop_scale)
+            c["fusion"][i] = None        # the layer's saved activations go before the next layer allocates
+        self._inputs_bwd(prep, c, dyf)
+
+    def _heads_bwd(self, prep, c, dlogits, dvalues, dfull_logits):
+        """actor / critic heads, output projection and final RMSNorm -> the gradient of the decoder's output rows (None: no head received a gradient)"""
+        D, T, B, R, g = self.D, prep.T, prep.B, prep.R, self.g
+        dbel = torch.empty(R, D, device=self.device_, dtype=F32)
+        acc = False      # the first head that has a gradient writes dbel, the next one adds to it
+        for head, dy in ((self.actor.linear, dlogits),) + (((self.critic.fc, dvalues),) if self.critic_type == "linear" else ()):
+            if dy is not None:
+                ops.small_linear_bwd(c["beliefs"], head.weight, dy.reshape(R, -1).contiguous(), dbel, g(head.weight), g(head.bias), T, B, accumulate_dx=acc)
+                acc = True
+        if self.critic_type != "linear" and (dvalues is not None or dfull_logits is not None):
+            self._critic_head_bwd(c["head"], T, B, dvalues, dfull_logits, dbel, accumulate_dx=acc)
+            acc = True
+        if not acc:
+            return None
+        dy = torch.empty(R, D, device=self.device_, dtype=self.adt)
         ops.cast_bf16(dbel, dy)
-        ops.gemm_tn_acc(dy, c["nf"], dw["dout"], R, D, D)
-        dnf = ops.gemm_nt(dy, wt["dout"], R, D, D)
-        dx = ops.norm_bwd(dnf, c["xd_last"], self.decoder.norm.weight, None, None, c["rf"], R, g(self.decoder.norm.weight), None, rms=True, D=D)
+        ops.gemm_tn_acc(dy, c["nf"], self._dw["dout"], R, D, D)
+        dnf = ops.gemm_nt(dy, self._wt["dout"], R, D, D)
+        return ops.norm_bwd(dnf, c["xd_last"], self.decoder.norm.weight, None, None, c["rf"], R, g(self.decoder.norm.weight), None, rms=True, D=D)
+
+    def _decoder_seq_bwd(self, prep, c, dx):
+        """backward of ``_decoder_seq_fwd``: gradient of the decoder's output rows -> gradient of its input rows"""
+        D, HD, T, B, R, wt, dw, g, SCD = self.D, self.dec_hidden, prep.T, prep.B, prep.R, self._wt, self._dw, self.g, self.hdim_dec ** -0.5
         for i in reversed(range(len(self.decoder.layers))):
             l, a = self.decoder.layers[i], c["dec"][i]
             ops.gemm_tn_acc(dx, a["g"], dw[f"d{i}.w2"], R, D, HD)
@@ -599,106 +653,90 @@ class Tower(nn.Module):
             dh = ops.norm_bwd(dn2, a["h"], l.ffn_norm.weight, None, None, a["r2"], R, g(l.ffn_norm.weight), None, rms=True, dres=dx, D=D)
             ops.gemm_tn_acc(dh, a["ao"], dw[f"d{i}.wo"], R, D, D)
             dao = ops.gemm_nt(dh, wt[f"d{i}.wo"], R, D, D)
-            dqkv = torch.empty(R, 3 * D, device=dev, dtype=self.adt)
+            dqkv = torch.empty(R, 3 * D, device=self.device_, dtype=self.adt)
             q = a["qkv"]
             ops.attn_bwd(q, q[:, D:], q[:, 2 * D:], 3 * D, a["ao"], D, a["lse"], dao, D, dqkv, dqkv[:, D:], dqkv[:, 2 * D:], 3 * D,
                          B, T, self.Hdec, SCD, mask_mode=ops.MASK_BLOCK_CAUSAL, traj=prep.traj_bt, head_dim=self.hdim_dec)
             ops.gemm_tn_acc(dqkv, a["n1"], dw[f"d{i}.qkv"], R, 3 * D, D)
             dn1 = ops.gemm_nt(dqkv, wt[f"d{i}.qkv"], R, D, 3 * D)
             dx = ops.norm_bwd(dn1, a["x"], l.attention_norm.weight, None, None, a["r1"], R, g(l.attention_norm.weight), None, rms=True, dres=dh, D=D)
-        pruned = bool(c["fusion"]) and c["fusion"][-1]["pruned"]
-        if pruned:
-            dxf = torch.empty(R, D, device=dev, dtype=self.adt)        # gradient of the position-0 outputs only
-            ops.decoder_embed_bwd(dx, prep.prev_actions, prep.masks, prep.hand, T, B, dxf, D, g(self.last_actions_embed.weight),
-                                  g(self.object_in_hand_embed.weight))
-            dyf = dxf
-        else:
-            dxf = ops.zeros(R, S, D, device=dev, dtype=self.adt)
-            ops.decoder_embed_bwd(dx, prep.prev_actions, prep.masks, prep.hand, T, B, dxf, S * D, g(self.last_actions_embed.weight),
-                                  g(self.object_in_hand_embed.weight))
-            dyf = dxf.view(M, D)
-        site = self._site_fn(c.get("drop_seed"))
-        drop_scale = 1.0 / (1.0 - self.dropout_p) if c.get("drop_seed") is not None else 1.0
-        def masked_like(t, on):   # second norm_bwd output: the gradient of the dropped-out sub-layer output
-            return torch.empty_like(t) if on else None
-        for i in reversed(range(len(ve.fusion_xformer.layers))):
-            l, a = ve.fusion_xformer.layers[i], c["fusion"][i]
-            if a["pruned"]:
-                d3, d1 = site(i, 3, S), site(i, 1, S)
-                df = masked_like(a["h2"], d3 is not None)
-                dh2 = ops.norm_bwd(dyf, a["h2"], l.norm2.weight, l.norm2.bias, a["n2"][0], a["n2"][1], R, g(l.norm2.weight), g(l.norm2.bias),
-                                   dx_drop=df, drop=d3, D=D)
-                df = dh2 if df is None else df           # grad of linear2's output (through dropout2); dh2 = residual-path grad
-                ops.gemm_tn_acc(df, a["f1"], dw[f"f{i}.l2"], R, D, 2048, db=g(l.linear2.bias))
-                # f1 is stored after ReLU and dropout: f1 > 0 <=> (pre-activation > 0 and kept); alpha = the dropout scale
-                df1 = ops.gemm_nt(df, wt[f"f{i}.l2"], R, 2048, D, relu_mask=a["f1"], alpha=drop_scale)
-                ops.gemm_tn_acc(df1, a["x1"], dw[f"f{i}.l1"], R, 2048, D, db=g(l.linear1.bias))
-                dx1 = ops.gemm_nt(df1, wt[f"f{i}.l1"], R, D, 2048, residual=dh2)
-                da = masked_like(a["h1"], d1 is not None)
-                dh1 = ops.norm_bwd(dx1, a["h1"], l.norm1.weight, l.norm1.bias, a["n1"][0], a["n1"][1], R, g(l.norm1.weight), g(l.norm1.bias),
-                                   dx_drop=da, drop=d1, D=D)
-                da = dh1 if da is None else da
-                ops.gemm_tn_acc(da, a["ao"], dw[f"f{i}.out"], R, D, D, db=g(l.self_attn.out_proj.bias))
-                dao = ops.gemm_nt(da, wt[f"f{i}.out"], R, D, D)
-                gb = g(l.self_attn.in_proj_bias)
-                if a["absorbed"]:
-                    # backward of the absorbed form (run_forward): dc_h = W_v,h^T do_h, dsigma_h = do_h . b_v,h; the streaming kernel returns dX of every token
-                    # and dqt; every weight gradient goes through the accumulating GEMM / column sum (deterministic mode included).  The K third of the bias
-                    # gradient is exactly zero (sum_j dS_hj = 0) and is not touched.
-                    w_in, wt_in, dw_in = w[f"f{i}.in"], wt[f"f{i}.in"], dw[f"f{i}.in"]
-                    edao, dsig, sdao = ops.head_expand(dao, R, bias=l.self_attn.in_proj_bias[2 * D:], sigma=a["sig"])
-                    dcc = ops.gemm_nt(edao, wt_in[:, 2 * D:], 8 * R, D, D)
-                    ops.gemm_tn_acc(edao, a["cc"], dw_in[2 * D:], 8 * R, D, D)                   # dW_v,h += do_h c_h^T
-                    ops.colsum_acc(sdao, gb[2 * D:], R, D)                                       # db_v,h += sigma_h do_h
-                    dyf, dqt = ops.attn_q1_bwd(a["x"], S * D, a["qt"], dcc, dsig, a["prob"], R, S, SCF, drop=site(i, 0))
-                    dyf = dyf.view(M, D)
-                    ops.gemm_tn_acc(a["eq"], dqt, dw_in[D:2 * D], 8 * R, D, D)                   # dW_k,h += q_h dqt_h^T
-                    dq0 = ops.head_pick(ops.gemm_nt(dqt, w_in[D:2 * D], 8 * R, D, D), R)         # W_k,h dqt_h
-                    ops.gemm_tn_acc(dq0, a["x"], dw_in[:D], R, D, D, ldx=S * D, db=gb[:D])
-                else:
-                    dq0 = torch.empty(R, D, device=dev, dtype=self.adt)
-                    dkv = torch.empty(M, 2 * D, device=dev, dtype=self.adt)
-                    kv = a["kv"]
-                    ops.attn_bwd(a["q0"], kv, kv[:, D:], 2 * D, a["ao"], D, a["lse"], dao, D, dq0, dkv, dkv[:, D:], 2 * D, R, S, H, SCF, head_dim=self.hdim,
-                                 Sq=1, ldq=D, lddq=D, drop=site(i, 0))
-                    ops.gemm_tn_acc(dkv, a["x"], dw[f"f{i}.in"][D:], M, 2 * D, D, db=gb[D:])
-                    ops.gemm_tn_acc(dq0, a["x"], dw[f"f{i}.in"][:D], R, D, D, ldx=S * D, db=gb[:D])
-                    dyf = ops.gemm_nt(dkv, wt[f"f{i}.in"][:, D:], M, D, 2 * D)                   # dX through K and V, all tokens
-                t0 = ops.gemm_nt(dq0, wt[f"f{i}.in"][:, :D], R, D, D, residual=dh1)             # position 0: Q path + residual path
-                ops.rows_add(dyf, S * D, t0, D, R, D)
-                c["fusion"][i] = None
-                continue
-            d3, d1 = site(i, 3), site(i, 1)
-            df = masked_like(a["h2"], d3 is not None)
-            dh2 = ops.norm_bwd(dyf, a["h2"], l.norm2.weight, l.norm2.bias, a["n2"][0], a["n2"][1], M, g(l.norm2.weight), g(l.norm2.bias),
-                               dx_drop=df, drop=d3, D=D)
-            df = dh2 if df is None else df               # grad of linear2's output (through dropout2); dh2 = residual-path grad
-            ops.gemm_tn_acc(df, a["f1"], dw[f"f{i}.l2"], M, D, 2048, db=g(l.linear2.bias))
-            # the sign bits were taken after ReLU and dropout: bit <=> (pre-activation > 0 and kept); alpha = the dropout scale
-            if a["f1b"] is not None:
-                df1 = ops.gemm_nt(df, wt[f"f{i}.l2"], M, 2048, D, relu_bits=a["f1b"], alpha=drop_scale)
-            else:       # fp32 verification mode: the stored activation itself is the mask
-                df1 = ops.gemm_nt(df, wt[f"f{i}.l2"], M, 2048, D, relu_mask=a["f1"], alpha=drop_scale)
-            ops.gemm_tn_acc(df1, a["x1"], dw[f"f{i}.l1"], M, 2048, D, db=g(l.linear1.bias))
-            dx1 = ops.gemm_nt(df1, wt[f"f{i}.l1"], M, D, 2048, residual=dh2)
-            del df1, df
-            da = masked_like(a["h1"], d1 is not None)
-            dh1 = ops.norm_bwd(dx1, a["h1"], l.norm1.weight, l.norm1.bias, a["n1"][0], a["n1"][1], M, g(l.norm1.weight), g(l.norm1.bias),
-                               dx_drop=da, drop=d1, D=D)
-            da = dh1 if da is None else da
-            ops.gemm_tn_acc(da, a["ao"], dw[f"f{i}.out"], M, D, D, db=g(l.self_attn.out_proj.bias))
-            dao = ops.gemm_nt(da, wt[f"f{i}.out"], M, D, D)
-            dqkv = torch.empty(M, 3 * D, device=dev, dtype=self.adt)
-            q = a["qkv"]
-            if a.get("f8") is not None:
-                ops.attn_fp8_bwd(a["f8"], a["ao"], a["lse"], dao, dqkv, dqkv[:, D:], dqkv[:, 2 * D:], 3 * D, SCF, drop=site(i, 0))
+        return dx
+
+    @staticmethod
+    def _relu_bwd_gemm(dy, wt, rows, n, k, act, bits, alpha=1.0):
+        """alpha * (dy @ wt^T) where the forward's ReLU output ``act`` was positive: by its sign ``bits`` if the forward kept them, else by the stored activation (fp32 mode, pruned rows)"""
+        return ops.gemm_nt(dy, wt, rows, n, k, alpha=alpha, **(dict(relu_bits=bits) if bits is not None else dict(relu_mask=act)))
+
+    def _fusion_post_bwd(self, i, a, dyf, rows, row_mult, site, drop_scale):
+        """backward of ``_fusion_post_fwd``: gradient of the layer's output rows -> (dao, dh1), the gradients of the attention output and of the residual path into its input"""
+        D, F, wt, dw, g, l = self.D, self.dff, self._wt, self._dw, self.g, self.visual_encoder.fusion_xformer.layers[i]
+        d3, d1 = site(i, 3, row_mult), site(i, 1, row_mult)
+        df = torch.empty_like(a["h2"]) if d3 is not None else None      # under dropout norm_bwd has a second output: the gradient of the dropped-out sub-layer output
+        dh2 = ops.norm_bwd(dyf, a["h2"], l.norm2.weight, l.norm2.bias, a["n2"][0], a["n2"][1], rows, g(l.norm2.weight), g(l.norm2.bias),
+                           dx_drop=df, drop=d3, D=D)
+        df = dh2 if df is None else df               # grad of linear2's output (through dropout2); dh2 = residual-path grad
+        ops.gemm_tn_acc(df, a["f1"], dw[f"f{i}.l2"], rows, D, F, db=g(l.linear2.bias))
+        # f1 and its sign bits were taken after ReLU and dropout: positive <=> (pre-activation > 0 and kept); alpha = the dropout scale
+        df1 = self._relu_bwd_gemm(df, wt[f"f{i}.l2"], rows, F, D, a["f1"], a["f1b"], alpha=drop_scale)
+        ops.gemm_tn_acc(df1, a["x1"], dw[f"f{i}.l1"], rows, F, D, db=g(l.linear1.bias))
+        dx1 = ops.gemm_nt(df1, wt[f"f{i}.l1"], rows, D, F, residual=dh2)
+        del df1, df                                  # [rows, dff]: freed before the next allocation
+        da = torch.empty_like(a["h1"]) if d1 is not None else None
+        dh1 = ops.norm_bwd(dx1, a["h1"], l.norm1.weight, l.norm1.bias, a["n1"][0], a["n1"][1], rows, g(l.norm1.weight), g(l.norm1.bias),
+                           dx_drop=da, drop=d1, D=D)
+        da = dh1 if da is None else da
+        ops.gemm_tn_acc(da, a["ao"], dw[f"f{i}.out"], rows, D, D, db=g(l.self_attn.out_proj.bias))
+        return ops.gemm_nt(da, wt[f"f{i}.out"], rows, D, D), dh1
+
+    def _fusion_layer_bwd(self, i, a, dyf, prep, site, drop_scale):
+        """Backward of fusion layer ``i``: the gradient of its output rows -> the gradient of its input rows [R * S, D]"""
+        D, H, R, S, w, wt, dw, g, SCF = self.D, self.H, prep.R, prep.S, self._w, self._wt, self._dw, self.g, self.hdim ** -0.5
+        M, l = R * S, self.visual_encoder.fusion_xformer.layers[i]
+        if a["pruned"]:
+            dao, dh1 = self._fusion_post_bwd(i, a, dyf, R, S, site, drop_scale)
+            gb = g(l.self_attn.in_proj_bias)
+            if a["absorbed"]:
+                # backward of the absorbed form (_fusion_layer_fwd): dc_h = W_v,h^T do_h, dsigma_h = do_h . b_v,h; the streaming kernel returns dX of every token
+                # and dqt; every weight gradient goes through the accumulating GEMM / column sum (deterministic mode included).  The K third of the bias
+                # gradient is exactly zero (sum_j dS_hj = 0) and is not touched.
+                w_in, wt_in, dw_in = w[f"f{i}.in"], wt[f"f{i}.in"], dw[f"f{i}.in"]
+                edao, dsig, sdao = ops.head_expand(dao, R, bias=l.self_attn.in_proj_bias[2 * D:], sigma=a["sig"])
+                dcc = ops.gemm_nt(edao, wt_in[:, 2 * D:], 8 * R, D, D)
+                ops.gemm_tn_acc(edao, a["cc"], dw_in[2 * D:], 8 * R, D, D)                   # dW_v,h += do_h c_h^T
+                ops.colsum_acc(sdao, gb[2 * D:], R, D)                                       # db_v,h += sigma_h do_h
+                dx, dqt = ops.attn_q1_bwd(a["x"], S * D, a["qt"], dcc, dsig, a["prob"], R, S, SCF, drop=site(i, 0))
+                dx = dx.view(M, D)
+                ops.gemm_tn_acc(a["eq"], dqt, dw_in[D:2 * D], 8 * R, D, D)                   # dW_k,h += q_h dqt_h^T
+                dq0 = ops.head_pick(ops.gemm_nt(dqt, w_in[D:2 * D], 8 * R, D, D), R)         # W_k,h dqt_h
+                ops.gemm_tn_acc(dq0, a["x"], dw_in[:D], R, D, D, ldx=S * D, db=gb[:D])
             else:
-                ops.attn_bwd(q, q[:, D:], q[:, 2 * D:], 3 * D, a["ao"], D, a["lse"], dao, D, dqkv, dqkv[:, D:], dqkv[:, 2 * D:], 3 * D,
-                             R, S, H, SCF, drop=site(i, 0), head_dim=self.hdim)
-            ops.gemm_tn_acc(dqkv, a["x"], dw[f"f{i}.in"], M, 3 * D, D, db=g(l.self_attn.in_proj_bias))
-            dyf = ops.gemm_nt(dqkv, wt[f"f{i}.in"], M, D, 3 * D, residual=dh1)
-            c["fusion"][i] = None
-        dx0 = dyf
+                dq0 = torch.empty(R, D, device=self.device_, dtype=self.adt)
+                dkv = torch.empty(M, 2 * D, device=self.device_, dtype=self.adt)
+                kv = a["kv"]
+                ops.attn_bwd(a["q0"], kv, kv[:, D:], 2 * D, a["ao"], D, a["lse"], dao, D, dq0, dkv, dkv[:, D:], 2 * D, R, S, H, SCF, head_dim=self.hdim,
+                             Sq=1, ldq=D, lddq=D, drop=site(i, 0))
+                ops.gemm_tn_acc(dkv, a["x"], dw[f"f{i}.in"][D:], M, 2 * D, D, db=gb[D:])
+                ops.gemm_tn_acc(dq0, a["x"], dw[f"f{i}.in"][:D], R, D, D, ldx=S * D, db=gb[:D])
+                dx = ops.gemm_nt(dkv, wt[f"f{i}.in"][:, D:], M, D, 2 * D)                    # dX through K and V, all tokens
+            t0 = ops.gemm_nt(dq0, wt[f"f{i}.in"][:, :D], R, D, D, residual=dh1)             # position 0: Q path + residual path
+            ops.rows_add(dx, S * D, t0, D, R, D)
+            return dx
+        dao, dh1 = self._fusion_post_bwd(i, a, dyf, M, 1, site, drop_scale)
+        dqkv = torch.empty(M, 3 * D, device=self.device_, dtype=self.adt)
+        q = a["qkv"]
+        if a["f8"] is not None:
+            ops.attn_fp8_bwd(a["f8"], a["ao"], a["lse"], dao, dqkv, dqkv[:, D:], dqkv[:, 2 * D:], 3 * D, SCF, drop=site(i, 0))
+        else:
+            ops.attn_bwd(q, q[:, D:], q[:, 2 * D:], 3 * D, a["ao"], D, a["lse"], dao, D, dqkv, dqkv[:, D:], dqkv[:, 2 * D:], 3 * D,
+                         R, S, H, SCF, drop=site(i, 0), head_dim=self.hdim)
+        ops.gemm_tn_acc(dqkv, a["x"], dw[f"f{i}.in"], M, 3 * D, D, db=g(l.self_attn.in_proj_bias))
+        return ops.gemm_nt(dqkv, wt[f"f{i}.in"], M, D, 3 * D, residual=dh1)
+
+    def _inputs_bwd(self, prep, c, dx0):
+        """backward of ``_inputs_fwd``: gradient of the fusion transformer's input rows -> fusion token, text adapter (frozen text encoder), visual adapter + compressor"""
+        D, T, B, R, S, L, U = self.D, prep.T, prep.B, prep.R, prep.S, prep.L, prep.U
+        ve, wt, dw, g, dev = self.visual_encoder, self._wt, self._dw, self.g, self.device_
+        M2 = R * 2 * NPATCH
         ops.colsum_acc(dx0, g(ve.fusion_token), R, D, row_stride=S)
         # text adapter (trainable) -- the T5 encoder is frozen (no_grad in the reference)
         dtf = ops.zeros(U * L, D, device=dev, dtype=F32)
@@ -722,9 +760,9 @@ class Tower(nn.Module):
                            g(ve.visual_adapter[1].weight), g(ve.visual_adapter[1].bias), relu=True, dtok=self._dcamtok,
                            tok_group=NPATCH, dymap=(2 * NPATCH, S, 1), D=D)
         ops.gemm_tn_acc(da1, c["c2"], dw["va"], M2, D, D, db=g(ve.visual_adapter[0].bias))
-        dc2 = ops.gemm_nt(da1, wt["va"], M2, D, D, relu_bits=c["c2b"]) if c.get("c2b") is not None else ops.gemm_nt(da1, wt["va"], M2, D, D, relu_mask=c["c2"])
+        dc2 = self._relu_bwd_gemm(da1, wt["va"], M2, D, D, c["c2"], c["c2b"])
         ops.gemm_tn_acc(dc2, c["c1"], dw["c2"], M2, D, D, db=g(ve.visual_compressor[2].bias))
-        dc1 = ops.gemm_nt(dc2, wt["c2"], M2, D, D, relu_bits=c["c1b"]) if c.get("c1b") is not None else ops.gemm_nt(dc2, wt["c2"], M2, D, D, relu_mask=c["c1"])
+        dc1 = self._relu_bwd_gemm(dc2, wt["c2"], M2, D, D, c["c1"], c["c1b"])
         ops.gemm_tn_acc(dc1, prep.tokens.view(M2, self.dino_dim), dw["c1"], M2, D, self.dino_dim, db=g(ve.visual_compressor[0].bias))
 
 
@@ -736,7 +774,7 @@ class T5Frozen(nn.Module):
     def __init__(self, device, vocab=32128, d=512, h=8, dff=2048, n_layers=6, buckets=32, max_distance=128):
         super().__init__()
         self.device_ = device
-        self.h, self.buckets, self.max_distance = h, buckets, max_distance
+        self.h, self.dff, self.buckets, self.max_distance = h, dff, buckets, max_distance
 
         def P(*shape, scale=None):
             t = torch.randn(*shape) * (scale if scale is not None else 1.0 / math.sqrt(shape[-1]))
@@ -761,7 +799,7 @@ class T5Frozen(nn.Module):
             self.encoder.block.append(b)
         self.encoder.final_layer_norm = _NS()
         self.encoder.final_layer_norm.weight = nn.Parameter(torch.ones(d, device=device), requires_grad=False)
-        self._rt = None
+        self._rt = self._rt_dtype = None
         self._bias_cache: Dict[int, torch.Tensor] = {}
 
     def sync(self, dtype=BF16):
@@ -805,7 +843,7 @@ class T5Frozen(nn.Module):
         (allenact_dino_transformer.py:193) switches HF T5's dropout 0.1 on too -- so in train mode its six
         dropout sites per block / stack are applied here as well.  One realisation per unique goal and forward pass (the reference
         re-encodes the goal for every (t, b) row and so draws a fresh mask per row)."""
-        if self._rt is None or getattr(self, "_rt_dtype", BF16) != dtype:
+        if self._rt is None or self._rt_dtype != dtype:
             self.sync(dtype)
         U, L = ids.shape
         n = U * L
@@ -830,11 +868,11 @@ class T5Frozen(nn.Module):
                                  drop=site(s0))
             x = ops.gemm_nt(ao, rt["o"], n, D, D, residual=x, drop=site(s0 + 1))
             if fused:
-                hdn = ops.gemm_nt_rmsa(x, rt["wi_g"], n, 2048, D, 1e-6, act=ops.ACT_RELU, drop=site(s0 + 2))
+                hdn = ops.gemm_nt_rmsa(x, rt["wi_g"], n, self.dff, D, 1e-6, act=ops.ACT_RELU, drop=site(s0 + 2))
             else:
                 nrm, _, _ = ops.norm_fwd(x, b.layer[1].layer_norm.weight, None, 1e-6, n, rms=True, save_stats=False)
-                hdn = ops.gemm_nt(nrm, rt["wi"], n, 2048, D, act=ops.ACT_RELU, drop=site(s0 + 2))
-            x = ops.gemm_nt(hdn, rt["wo"], n, D, 2048, residual=x, drop=site(s0 + 3))
+                hdn = ops.gemm_nt(nrm, rt["wi"], n, self.dff, D, act=ops.ACT_RELU, drop=site(s0 + 2))
+            x = ops.gemm_nt(hdn, rt["wo"], n, D, self.dff, residual=x, drop=site(s0 + 3))
         out, _, _ = ops.norm_fwd(x, self.encoder.final_layer_norm.weight, None, 1e-6, n, rms=True, save_stats=False)
         ops.dropout_(out, site(63))
         return out
@@ -842,8 +880,24 @@ class T5Frozen(nn.Module):
 
 # ================================================================================================ shared per-call inputs
 class Prep:
-    """Per-forward inputs shared by the three towers (built once)."""
-    pass
+    """Per-forward inputs shared by the three towers (built once).  Producers fill the fields one by one; a name that is not declared here is an AttributeError.
+    R = T * B rows of S fusion tokens; U unique goals of L tokens; tokens [R, 2, 84, dino_dim]; prev_actions, masks, hand, time_step [R]; traj_bt [B, T]; ids,
+    attn_mask [U, L]; gid [R]: row -> goal.  Optional: ``acting`` (a T = 1 pass under no_grad is a step against the KV caches), ``ids_key`` (host-side identity of
+    the goals: eval-mode text-feature cache), ``attn_mask_u8`` (attn_mask in the kernels' format), ``kvalid_static`` (recorded steps: the KV-window mask [B, max_steps])."""
+    __slots__ = ("T", "B", "R", "S", "L", "U", "tokens", "prev_actions", "masks", "hand", "time_step", "traj_bt", "ids", "attn_mask", "gid",
+                 "acting", "ids_key", "attn_mask_u8", "kvalid_static")
+
+    def __init__(self):
+        self.acting, self.ids_key, self.attn_mask_u8, self.kvalid_static = True, None, None, None
+
+
+class _ActingState(Prep):
+    """A recorded / captured acting step: the Prep fields are its static input buffers; + device-resident step counter and indices, graph or per-tower plans, outputs, grouped replays"""
+    __slots__ = ("t_dev", "ar_steps", "graph", "plans", "outs", "gplans", "grouped_ok")
+
+    def __init__(self):
+        super().__init__()
+        self.graph, self.plans, self.outs, self.gplans, self.grouped_ok = None, None, None, {}, False
 
 
 class _TowerFn(torch.autograd.Function):
@@ -895,8 +949,7 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
                           hand=an_object_is_in_hand_uuid, time=time_step_uuid, traj=traj_idx_uuid)
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
         # small shapes (acting steps, small-batch updates): towers on concurrent streams; SVLA_SERIAL_TOWERS=1 turns it off
-        import os as _os
-        self.concurrent_towers = _os.environ.get("SVLA_SERIAL_TOWERS", "0") != "1"
+        self.concurrent_towers = os.environ.get("SVLA_SERIAL_TOWERS", "0") != "1"
         self.concurrent_tower_tokens = 1 << 17          # rows x fusion tokens up to which the towers run concurrently
         # Train-mode dropout inside the frozen T5 encoder: by default one realisation per UNIQUE goal per forward (the encoder runs once per
         # unique goal); the reference draws one per (t, b) row (it encodes every row).  True = the reference's statistics, at the price of
@@ -905,7 +958,9 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         # recorded acting steps replay the three towers as grouped launches (ops.GroupedPlans); SVLA_GROUPED_TOWERS=0: the three-stream replay (A/B, tests)
         self.grouped_towers = os.environ.get("SVLA_GROUPED_TOWERS", "1") != "0"
         self._acting_graphs, self._acting_backend = None, "plan"
-        if self.concurrent_towers and precision == "bf16" and _os.environ.get("SVLA_NO_ACTING_PLANS", "0") != "1":
+        self._tower_streams = None                      # one HIP stream per tower (run_towers_concurrently)
+        self._invalidate_hooks = []                     # called by invalidate_recorded (the engine's recorded env-chunks)
+        if self.concurrent_towers and precision == "bf16" and os.environ.get("SVLA_NO_ACTING_PLANS", "0") != "1":
             self.enable_acting_plans(True)              # recorded single-step launches are the default acting path
         self._goal_cache: Dict[int, List[int]] = {}
         self.sync_weights()
@@ -963,9 +1018,9 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
 
     def invalidate_recorded(self):
         """Drop every recorded launch sequence / captured graph that may reference replaced tensors."""
-        if getattr(self, "_acting_graphs", None) is not None:
+        if self._acting_graphs is not None:
             self._acting_graphs.clear()
-        for hook in getattr(self, "_invalidate_hooks", []):
+        for hook in self._invalidate_hooks:
             hook()
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
@@ -1053,7 +1108,7 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         Inputs were produced on the current stream (side streams wait for it), outputs are handed back to it (it waits for the side
         streams; returned tensors are ``record_stream``-ed so the caching allocator does not recycle them early)."""
         main = torch.cuda.current_stream()
-        if getattr(self, "_tower_streams", None) is None:
+        if self._tower_streams is None:
             self._tower_streams = [torch.cuda.Stream(device=self.device_) for _ in self.towers]
         outs = []
         for k, (t, s) in enumerate(zip(self.towers, self._tower_streams)):
@@ -1092,31 +1147,20 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         plan_mode = self._acting_backend == "plan"
         for t in self.towers:
             t._ensure_caches(B)
-        key = (B, L, self.training, self._acting_backend, tuple(getattr(t, "_kv_version", 0) for t in self.towers))
+        key = (B, L, self.training, self._acting_backend, tuple(t._kv_version for t in self.towers))
         st = self._acting_graphs.get(key)
         dev = self.device_
         if st is None:
-            st = Prep()
+            st = _ActingState()
             st.T, st.B, st.R, st.U, st.L, st.S = 1, B, B, B, L, TEXT_OFF + L
-            st.tokens = torch.zeros(B, 2, NPATCH, self.dino_dim, device=dev, dtype=self.adt)
-            st.prev_actions = torch.zeros(B, device=dev, dtype=torch.int64)
-            st.masks = torch.zeros(B, device=dev, dtype=F32)
-            st.hand = torch.zeros(B, device=dev, dtype=torch.int64)
-            st.time_step = torch.zeros(B, device=dev, dtype=torch.int64)
-            st.traj_bt = torch.zeros(B, 1, device=dev, dtype=torch.int32)
-            st.ids = torch.zeros(B, L, device=dev, dtype=torch.int64)
-            st.attn_mask = torch.ones(B, L, device=dev, dtype=torch.int64)
-            st.gid = torch.arange(B, device=dev, dtype=torch.int32)
-            st.t_dev = torch.zeros((), device=dev, dtype=torch.int64)
-            st.attn_mask_u8 = torch.ones(B, L, device=dev, dtype=torch.uint8)
-            st.kvalid_static = torch.zeros(B, self.max_steps, device=dev, dtype=torch.uint8) if plan_mode else None
+            z = lambda *shape, dtype=torch.int64: torch.zeros(*shape, device=dev, dtype=dtype)
+            st.tokens, st.prev_actions, st.masks, st.hand, st.time_step = z(B, 2, NPATCH, self.dino_dim, dtype=self.adt), z(B), z(B, dtype=F32), z(B), z(B)
+            st.traj_bt, st.ids, st.attn_mask = z(B, 1, dtype=torch.int32), z(B, L), torch.ones(B, L, device=dev, dtype=torch.int64)
+            st.gid, st.t_dev, st.attn_mask_u8 = torch.arange(B, device=dev, dtype=torch.int32), z(()), torch.ones(B, L, device=dev, dtype=torch.uint8)
+            st.kvalid_static = z(B, self.max_steps, dtype=torch.uint8) if plan_mode else None
             st.ar_steps = torch.arange(self.max_steps, device=dev)
-            st.graph = st.plans = None
-            for k, t in enumerate(self.towers):
-                t._ensure_caches(B)
+            for t in self.towers:
                 t._ar_steps = torch.arange(t.max_steps, device=dev)
-                if getattr(t, "_seed_dev_buf", None) is None:
-                    t._seed_dev_buf = torch.tensor([(t.drop_seed_base * 0x9E3779B1) & 0x7FFFFFFF], device=dev, dtype=torch.int32)
             for k_old in [k_ for k_ in self._acting_graphs if k_[4] != key[4]]:      # plans of replaced KV caches keep B x max_steps x 1024 x layers x 3 alive
                 del self._acting_graphs[k_old]
             self._acting_graphs[key] = st
@@ -1132,46 +1176,28 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
             # recorded step: every tower attends to cache slots [max(t - time_step_b, 0), t] (allenact_dino_transformer.py:388-397), computed once
             tc, ar = self.time_step_counter, st.ar_steps
             st.kvalid_static.copy_((ar[None, :] <= tc) & (ar[None, :] >= torch.clamp(tc - st.time_step, min=0)[:, None]))
+            for t in self.towers:
+                t.advance_device_seed()                  # fresh dropout noise per step: recorded, grouped or three-stream
             if st.plans is None:
-                for t in self.towers:
-                    t._ensure_caches(B)
-                versions = tuple(getattr(t, "_kv_version", 0) for t in self.towers)
+                versions = tuple(t._kv_version for t in self.towers)
 
                 def rec(k, t):
-                    plan = ops.LaunchPlan()
-                    t._t_dev, t._seed_dev = st.t_dev, t._seed_dev_buf
-                    keep = t.time_step_counter
-                    with plan:
-                        lg, vl, _ = t.run_forward(st, need_grad=False)
-                    t.time_step_counter = keep
-                    t._t_dev, t._seed_dev = None, None
-                    return plan, lg, vl
-                for t in self.towers:
-                    t._seed_dev_buf.add_(0x3C6EF35)
+                    with ops.LaunchPlan() as plan:
+                        return (plan,) + t.static_step(st)
                 res = self.run_towers_concurrently(rec)          # the recording pass is a real step
-                assert versions == tuple(getattr(t, "_kv_version", 0) for t in self.towers)
+                assert versions == tuple(t._kv_version for t in self.towers)
                 st.plans, st.outs = [r[0] for r in res], [(r[1], r[2]) for r in res]
-                st.gplans = {}
                 st.grouped_ok = ops.GroupedPlans.compatible(st.plans)
             elif self.grouped_towers and st.grouped_ok:
                 # tower-grouped replay (round 6): call i of the three recorded sequences is issued as ONE grid whose blockIdx.z picks the tower's
                 # arguments (csrc/launch.h) -- one dependency chain on the current stream instead of three chains on three streams, three times
                 # the workgroups per dispatch.  Same kernels, same arithmetic: bit-identical to the three-stream replay (tests/test_grouped_gpu.py)
-                for t in self.towers:
-                    t._seed_dev_buf.add_(0x3C6EF35)              # fresh dropout noise per step (device-resident seed, wraps in int32)
                 self._grouped_replay(st)
             else:
-                main = torch.cuda.current_stream()
-                for t in self.towers:
-                    t._seed_dev_buf.add_(0x3C6EF35)              # fresh dropout noise per step (device-resident seed, wraps in int32)
-                # one foreign call per tower (svla_replay_calls).  Host issue 2.0 -> 1.0 ms per step; the step itself is bound by the GPU side
-                # (~310 small dependent kernels on three streams: 3.0 ms), so issuing the three sequences from three host threads -- tried,
+                # one foreign call per tower (svla_replay_calls), each list on the stream it was recorded on.  Host issue 2.0 -> 1.0 ms per step; the step itself is
+                # bound by the GPU side (~310 small dependent kernels on three streams: 3.0 ms), so issuing the three sequences from three host threads -- tried,
                 # ctypes drops the GIL during the call -- changes nothing (21.4 k env-steps/s either way)
-                for plan, s_ in zip(st.plans, self._tower_streams):
-                    s_.wait_stream(main)
-                    plan.replay()
-                for s_ in self._tower_streams:
-                    main.wait_stream(s_)
+                self.run_towers_concurrently(lambda k, t: st.plans[k].replay())
             for t in self.towers:
                 t.time_step_counter += 1
             return st.outs[0][0].clone(), st.outs[1][1].clone(), st.outs[2][1].clone()
@@ -1179,13 +1205,8 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         def body():
             outs = []
             for t in self.towers:
-                t._t_dev, t._seed_dev = st.t_dev, t._seed_dev_buf
-                t._seed_dev_buf.add_(0x3C6EF35)          # fresh dropout noise per replay (wraps in int32)
-                keep = t.time_step_counter
-                lg, vl, _ = t.run_forward(st, need_grad=False)
-                t.time_step_counter = keep               # the host counter is advanced once per step below
-                t._t_dev, t._seed_dev = None, None
-                outs.append((lg, vl))
+                t.advance_device_seed()                  # fresh dropout noise per replay
+                outs.append(t.static_step(st))
             return outs
 
         if st.graph is None:
@@ -1216,16 +1237,16 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         KV-window mask, step counter, seed bumps) + the grouped replay -- no ``prepare``, none of the ~30 framework copies / compares the general path spends on a
         step.  Returns None whenever anything is not exactly as the recorded step expects (first step of a shape, other dtypes / layouts, string goals, a cache
         window about to wrap): the general path then handles -- and, if needed, records -- the step."""
-        if getattr(self, "_acting_graphs", None) is None or self._acting_backend != "plan" or not self.grouped_towers or torch.is_grad_enabled():
+        if self._acting_graphs is None or self._acting_backend != "plan" or not self.grouped_towers or torch.is_grad_enabled():
             return None
         tk, ids = observations.get("dino_tokens"), observations.get("goal_token_ids")
         if tk is None or ids is None or prev_actions.dim() != 2 or prev_actions.shape[0] != 1:
             return None
         B, L, tc = prev_actions.shape[1], ids.shape[-1], self.time_step_counter
-        if not (tc < self.max_steps - 1 and all(t.time_step_counter == tc and getattr(t, "_kv", None) is not None and t._kv[0].shape[0] >= B for t in self.towers)):
+        if not (tc < self.max_steps - 1 and all(t.time_step_counter == tc and t._kv is not None and t._kv[0].shape[0] >= B for t in self.towers)):
             return None
-        st = self._acting_graphs.get((B, L, self.training, self._acting_backend, tuple(getattr(t, "_kv_version", 0) for t in self.towers)))
-        if st is None or st.plans is None or not getattr(st, "grouped_ok", False):
+        st = self._acting_graphs.get((B, L, self.training, self._acting_backend, tuple(t._kv_version for t in self.towers)))
+        if st is None or st.plans is None or not st.grouped_ok:
             return None
         u = self.uuids
         hand, ts = observations.get(u["hand"]), observations.get(u["time"])
@@ -1237,7 +1258,7 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         for t in self.towers:
             t.refresh_folded()
         ops.acting_stage(tk, st.tokens, prev_actions, st.prev_actions, masks, st.masks, hand, st.hand, ts, st.time_step, ids, st.ids, st.attn_mask, st.attn_mask_u8,
-                         st.kvalid_static, st.t_dev, B, L, self.max_steps, tc, [t._seed_dev_buf for t in self.towers], 0x3C6EF35)
+                         st.kvalid_static, st.t_dev, B, L, self.max_steps, tc, [t._seed_dev_buf for t in self.towers], SEED_STEP)
         self._grouped_replay(st)
         for t in self.towers:
             t.time_step_counter += 1
@@ -1249,7 +1270,7 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         if fast is not None:
             return fast, memory
         prep = self.prepare(observations, prev_actions, masks)
-        if (prep.T == 1 and getattr(self, "_acting_graphs", None) is not None and not torch.is_grad_enabled()
+        if (prep.T == 1 and self._acting_graphs is not None and not torch.is_grad_enabled()
                 and self.time_step_counter < self.max_steps - 1 and all(t.time_step_counter == self.time_step_counter for t in self.towers)):
             logits, values, c_values = self._acting_step_graph(prep)
             return SafeActorCriticOutput(distributions=CategoricalDistr(logits), values=values, c_values=c_values, extras={}), memory
@@ -1258,11 +1279,10 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         if not torch.is_grad_enabled() and self.concurrent_towers and prep.R * prep.S <= self.concurrent_tower_tokens:
             (logits, _), (_, values), (_, c_values) = self.run_towers_concurrently(lambda k, t: t.run_forward(prep, need_grad=False)[:2])
             c_full = self.c_critic_tsfm._last_full_logits
-            extras = self._extras(c_values, c_full) if prep.T > 1 else {}
-            return SafeActorCriticOutput(distributions=CategoricalDistr(logits), values=values, c_values=c_values, extras=extras), memory
-        logits, _, _ = _TowerFn.apply(self._anchor, self, prep, True, False)
-        _, values, _ = _TowerFn.apply(self._anchor, self.critic_tsfm, prep, False, True)
-        _, c_values, c_full = _TowerFn.apply(self._anchor, self.c_critic_tsfm, prep, False, True)
+        else:
+            logits, _, _ = _TowerFn.apply(self._anchor, self, prep, True, False)
+            _, values, _ = _TowerFn.apply(self._anchor, self.critic_tsfm, prep, False, True)
+            _, c_values, c_full = _TowerFn.apply(self._anchor, self.c_critic_tsfm, prep, False, True)
         # the diagnostics in ``extras`` are consumed by the losses only (update batches); single-step acting forwards skip them
         extras = self._extras(c_values, c_full) if prep.T > 1 else {}
         return SafeActorCriticOutput(distributions=CategoricalDistr(logits), values=values, c_values=c_values, extras=extras), memory

@@ -16,6 +16,41 @@ MASK_NONE, MASK_BLOCK_CAUSAL = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
 
+def _pack_words(decl, args, stream=None):
+    """One recorded call's arguments as the 64-bit words svla_replay_calls / svla_replay_calls_grouped read (include/svla.h): pointers / integers by value,
+    float / double by bit pattern, per the header's declaration ``decl``.  ``stream`` given: it replaces the call's own stream argument."""
+    words = []
+    for (name, ct), v in zip(decl, args):
+        if stream is not None and name == "stream":
+            words.append(int(stream) & 0xFFFFFFFFFFFFFFFF)
+        elif ct is ctypes.c_float:
+            words.append(struct.unpack("<I", struct.pack("<f", float(v)))[0])
+        elif ct is ctypes.c_double:
+            words.append(struct.unpack("<Q", struct.pack("<d", float(v)))[0])
+        elif v is None:
+            words.append(0)
+        elif isinstance(v, ctypes.c_void_p):
+            words.append(int(v.value or 0))
+        else:
+            words.append(int(v) & 0xFFFFFFFFFFFFFFFF)
+    return words
+
+
+def _flatten_calls(plans, stream=None):
+    """The recorded calls of ``plans`` (same entry points, same order) for svla_replay_calls[_grouped]: their number, ids, argument-word offsets and, per plan, the words"""
+    L = lib()
+    ids, offs, words = [], [], [[] for _ in plans]
+    for i, (fn, _) in enumerate(plans[0].calls):
+        name = fn.__name__
+        ids.append(L.fn_ids[name])
+        offs.append(len(words[0]))
+        for w, pl in zip(words, plans):
+            assert len(L.decls[name]) == len(pl.calls[i][1]), name
+            w += _pack_words(L.decls[name], pl.calls[i][1], stream)
+    arr = lambda ct, v: (ct * max(1, len(v)))(*v)
+    return len(ids), arr(ctypes.c_int, ids), arr(ctypes.c_int, offs), [arr(ctypes.c_ulonglong, w) for w in words]
+
+
 class LaunchPlan:
     """A recorded sequence of C-ABI calls (bound function + fully converted arguments, stream handle included) that can be re-issued from
     one tight loop: no tensor allocation, no wrapper code, no argument conversion.  Everything a recorded call touched -- tensors, dropout
@@ -42,31 +77,9 @@ class LaunchPlan:
     def compile(self):
         """Flatten the recorded calls for svla_replay_calls (include/svla.h): one FFI crossing per replay instead of one per launch.
         Arguments become 64-bit words -- pointers / integers by value, float / double by bit pattern, per the header's declaration."""
-        L = lib()
-        ids, offs, words = [], [], []
-        for fn, a in self.calls:
-            name = fn.__name__
-            decl = L.decls[name]
-            assert len(decl) == len(a), name
-            ids.append(L.fn_ids[name])
-            offs.append(len(words))
-            for (_, ct), v in zip(decl, a):
-                if ct is ctypes.c_float:
-                    words.append(struct.unpack("<I", struct.pack("<f", float(v)))[0])
-                elif ct is ctypes.c_double:
-                    words.append(struct.unpack("<Q", struct.pack("<d", float(v)))[0])
-                elif v is None:
-                    words.append(0)
-                elif isinstance(v, ctypes.c_void_p):
-                    words.append(int(v.value or 0))
-                else:
-                    words.append(int(v) & 0xFFFFFFFFFFFFFFFF)
-        self._n = len(ids)
-        self._ids = (ctypes.c_int * max(1, len(ids)))(*ids)
-        self._offs = (ctypes.c_int * max(1, len(offs)))(*offs)
-        self._words = (ctypes.c_ulonglong * max(1, len(words)))(*words)
+        self._n, self._ids, self._offs, (self._words,) = _flatten_calls([self])
         self._failed = ctypes.c_int(-1)
-        self._replay_fn = L.cdll.svla_replay_calls
+        self._replay_fn = lib().cdll.svla_replay_calls
         return self
 
     def replay(self):
@@ -94,39 +107,12 @@ class GroupedPlans:
 
     def __init__(self, plans, stream: int):
         assert self.compatible(plans)
-        L = lib()
         self.plans = list(plans)           # keeps the recorded tensors alive
-        ref = plans[0]
-        ids, offs, words = [], [], [[] for _ in plans]
-        for i, (fn, a) in enumerate(ref.calls):
-            name = fn.__name__
-            decl = L.decls[name]
-            ids.append(L.fn_ids[name])
-            offs.append(len(words[0]))
-            for m, pl in enumerate(plans):
-                am = pl.calls[i][1]
-                assert len(decl) == len(am), name
-                for (an, ct), v in zip(decl, am):
-                    if an == "stream":     # every launch of the group goes to the one stream the group is replayed on
-                        words[m].append(int(stream) & 0xFFFFFFFFFFFFFFFF)
-                    elif ct is ctypes.c_float:
-                        words[m].append(struct.unpack("<I", struct.pack("<f", float(v)))[0])
-                    elif ct is ctypes.c_double:
-                        words[m].append(struct.unpack("<Q", struct.pack("<d", float(v)))[0])
-                    elif v is None:
-                        words[m].append(0)
-                    elif isinstance(v, ctypes.c_void_p):
-                        words[m].append(int(v.value or 0))
-                    else:
-                        words[m].append(int(v) & 0xFFFFFFFFFFFFFFFF)
-        self._n, self._members = len(ids), len(plans)
-        self._stream = ctypes.c_void_p(int(stream))
-        self._ids = (ctypes.c_int * max(1, len(ids)))(*ids)
-        self._offs = (ctypes.c_int * max(1, len(offs)))(*offs)
-        self._words = [(ctypes.c_ulonglong * max(1, len(w)))(*w) for w in words]
+        self._n, self._ids, self._offs, self._words = _flatten_calls(plans, stream)      # every launch of the group goes to the one stream the group is replayed on
+        self._members, self._stream = len(plans), ctypes.c_void_p(int(stream))
         self._argv = (ctypes.POINTER(ctypes.c_ulonglong) * len(plans))(*[ctypes.cast(w, ctypes.POINTER(ctypes.c_ulonglong)) for w in self._words])
         self._failed = ctypes.c_int(-1)
-        self._fn = L.cdll.svla_replay_calls_grouped
+        self._fn = lib().cdll.svla_replay_calls_grouped
 
     @staticmethod
     def compatible(plans) -> bool:
