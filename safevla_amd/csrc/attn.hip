@@ -10,10 +10,8 @@
 // Layout trick ("swapped QK^T"): S^T = K.Q^T puts the query index on lane&15, so a query's whole score row is
 // lane-local (+2 cross-lane steps), and the probabilities already sit in the MFMA A-operand layout of P.V;
 // V (and K/Q/dO in the backward) are read as B operands straight from row-major LDS with ds_read_b64_tr_b16.
-#include "attn_common.h"      // dropout index, LDS swizzle and lane bases, fragment helpers: shared with the files below
-#include "attn_hd96.h"      // head_dim 96: its own kernels and LDS layout (attn_hd96.hip)
-#include "attn_long.h"      // backward for 256 < S <= 512: eight-wave kernels with runtime tile loops (attn_long.hip)
-#include "attn_decode_long.h"      // single-query forward for 512 < S <= 1024 (attn_decode_long.hip)
+#include "attn_host.h"      // the call record, the argument check and the launchers of the other families (attn_hd96.hip: head_dim 96; attn_long.hip: backward
+                            // for 256 < S <= 512; attn_decode_long.hip: single-query forward for 512 < S <= 1024); attn_common.h: the shared device helpers
 
 #define HD 64
 // LDS row (LDSROW, attn_common.h) = 128 B (one head slice row), 16-byte chunks XOR-swizzled: 48 KiB for two [192, 64] operands,
@@ -1273,33 +1271,24 @@ extern "C" int svla_attn_fwd_bf16(const bf16_t* Q, const bf16_t* K, const bf16_t
                                   int rows, int S, int H, int head_dim, float scale, int mask_mode, const int* traj,
                                   const float* bias, const unsigned char* kvalid, int Sq, long ldq, int kv_rows, const svla_dropout* drop,
                                   void* stream) {
-    if (head_dim == 96) return attn96_fwd_launch(Q, K, V, ld, O, ldo, LSE, rows, S, H, scale, mask_mode, traj, bias, kvalid, Sq, ldq, kv_rows, drop, stream);
+    AttnCall c{};
+    c.Q = Q; c.K = K; c.V = V; c.ld = ld; c.O = O; c.ldo = ldo; c.LSE = LSE;
+    c.rows = rows; c.S = S; c.H = H; c.scale = scale; c.mask_mode = mask_mode; c.traj = traj; c.bias = bias; c.kvalid = kvalid;
+    c.Sq = Sq; c.ldq = ldq; c.kv_rows = kv_rows; c.drop = drop; c.stream = (hipStream_t)stream;
+    if (head_dim == 96) return attn96_fwd_launch(c);
     if (head_dim == HD && S > 512) {
         // a cache window of up to 1024 slots exists for the single-query form only (csrc/attn_decode_long.hip: episodes of up to 1000 steps); every other form ends at 512
-        if (Sq != 1 || bias || mask_mode != MASK_NONE || drop_cfg(drop).thr || g_attn_no_decode) return SVLA_EINVAL;
-        return attn_decode_long_launch(Q, K, V, ld, O, ldo, LSE, rows, S, H, scale, kvalid, ldq, kv_rows > 0 ? kv_rows : S, stream);
+        if (Sq != 1 || mask_mode != MASK_NONE || drop_cfg(drop).thr || g_attn_no_decode) return SVLA_EINVAL;
+        return attn_decode_long_launch(c);
     }
-    if (head_dim != HD || rows <= 0 || S <= 0 || S > 512 || (ld % 8) || H <= 0 || (kv_rows > 0 && kv_rows < S)) return SVLA_EINVAL;
-    if (mask_mode == MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
-    if (Sq < 0 || Sq > S || (Sq > 0 && (ldq % 8))) return SVLA_EINVAL;
-    AttnArgs p{};
-    p.Q = Q; p.K = K; p.V = V; p.ld = ld; p.O = O; p.ldo = ldo; p.LSE = LSE; p.traj = traj; p.bias = bias; p.kvalid = kvalid;
-    p.S = S; p.H = H; p.mask_mode = mask_mode; p.scale = scale;
-    p.Sq = Sq > 0 ? Sq : S; p.ldq = Sq > 0 ? ldq : ld;
-    p.kv_rows = kv_rows > 0 ? kv_rows : S;
-    p.drop = drop_cfg(drop);
+    if (head_dim != HD || !attn_accepts(c, ATTN_FWD_64)) return SVLA_EINVAL;
+    AttnArgs p = attn_fill<AttnArgs>(c);
+    p.bias = bias; p.kv_rows = attn_kv_rows(c);
     p.xcd_rows = 0;      // (measured on the persistent forward: +1.5 % time with whole rows per XCD -- its next-item prefetch already hides the fetch; -1.4 % on the backward)
-    hipStream_t st = (hipStream_t)stream;
     if (p.Sq == 1 && !bias && mask_mode == MASK_NONE && !p.drop.thr && !g_attn_no_decode) {      // one query per row: read the valid keys only (KV-cached acting step)
-        return SVLA_LAUNCH(attn_decode_kernel, attn_decode_kernel_body, DEC_THREADS, 1, dim3(rows * H), dim3(DEC_THREADS), 0, st, p);
+        return SVLA_LAUNCH(attn_decode_kernel, attn_decode_kernel_body, DEC_THREADS, 1, dim3(rows * H), dim3(DEC_THREADS), 0, c.stream, p);
     }
-    if (S <= 64) return launch_fwd<4>(p, rows, st);
-    if (S <= 128) return launch_fwd<8>(p, rows, st);
-    if (S <= 192) return launch_fwd<12>(p, rows, st);
-    if (S <= 256) return launch_fwd<16>(p, rows, st);
-    if (S <= 288) return launch_fwd<18>(p, rows, st);
-    if (S <= 448) return launch_fwd<28>(p, rows, st);
-    return launch_fwd<32>(p, rows, st);
+    return attn_bucket<4, 8, 12, 16, 18, 28, 32>(S, [&](auto nkt) { return launch_fwd<nkt()>(p, rows, c.stream); });
 }
 
 extern "C" int svla_attn_bwd_bf16(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long ld, const bf16_t* O, long ldo,
@@ -1307,22 +1296,16 @@ extern "C" int svla_attn_bwd_bf16(const bf16_t* Q, const bf16_t* K, const bf16_t
                                   int rows, int S, int H, int head_dim, float scale, int mask_mode, const int* traj,
                                   const float* bias, const unsigned char* kvalid, int Sq, long ldq, long lddq, float* D_ws,
                                   const svla_dropout* drop, void* stream) {
-    if (head_dim == 96)
-        return attn96_bwd_launch(Q, K, V, ld, O, ldo, LSE, dO, lddo, dQ, dK, dV, ldd, rows, S, H, scale, mask_mode, traj, bias, kvalid, Sq, ldq, lddq, D_ws, drop, stream);
-    if (head_dim == HD && S > 256)      // 256 < S <= 512 (no bias): csrc/attn_long.hip; refuses S > 512 and the T5 bias itself
-        return attn_long_bwd_launch(Q, K, V, ld, O, ldo, LSE, dO, lddo, dQ, dK, dV, ldd, rows, S, H, scale, mask_mode, traj, bias, kvalid, Sq, ldq, lddq, D_ws, drop, stream);
-    if (head_dim != HD || rows <= 0 || S <= 0 || S > 256 || (ld % 8) || (lddo % 8) || H <= 0) return SVLA_EINVAL;
-    if (mask_mode == MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
-    if (Sq < 0 || Sq > S || (Sq > 0 && ((ldq % 8) || (lddq % 8)))) return SVLA_EINVAL;
-    AttnArgs p{};
-    p.Sq = Sq > 0 ? Sq : S; p.ldq = Sq > 0 ? ldq : ld; p.lddq = Sq > 0 ? lddq : ldd; p.kv_rows = S;
-    p.Q = Q; p.K = K; p.V = V; p.ld = ld; p.O = (bf16_t*)O; p.ldo = ldo; p.LSE = (float*)LSE; p.dO = dO; p.lddo = lddo;
-    p.dQ = dQ; p.dK = dK; p.dV = dV; p.ldd = ldd; p.traj = traj; p.bias = bias; p.kvalid = kvalid;
-    p.S = S; p.H = H; p.mask_mode = mask_mode; p.scale = scale; p.Dws = D_ws; p.drop = drop_cfg(drop);
+    AttnCall c{};
+    c.Q = Q; c.K = K; c.V = V; c.ld = ld; c.O = (bf16_t*)O; c.ldo = ldo; c.LSE = (float*)LSE; c.dO = dO; c.lddo = lddo;
+    c.dQ = dQ; c.dK = dK; c.dV = dV; c.ldd = ldd;
+    c.rows = rows; c.S = S; c.H = H; c.scale = scale; c.mask_mode = mask_mode; c.traj = traj; c.bias = bias; c.kvalid = kvalid;
+    c.Sq = Sq; c.ldq = ldq; c.lddq = lddq; c.D_ws = D_ws; c.drop = drop; c.stream = (hipStream_t)stream;
+    if (head_dim == 96) return attn96_bwd_launch(c);
+    if (head_dim == HD && S > 256) return attn_long_bwd_launch(c);      // 256 < S <= 512 (no bias): csrc/attn_long.hip; refuses S > 512 and the T5 bias itself
+    if (head_dim != HD || !attn_accepts(c, ATTN_BWD_64)) return SVLA_EINVAL;
+    AttnArgs p = attn_fill<AttnArgs>(c);
+    p.bias = bias; p.kv_rows = S; p.Dws = D_ws;
     p.xcd_rows = (g_attn_xcd_rows && H == 8) ? 1 : 0;
-    hipStream_t st = (hipStream_t)stream;
-    if (S <= 64) return launch_bwd<4>(p, rows, st);
-    if (S <= 128) return launch_bwd<8>(p, rows, st);
-    if (S <= 192) return launch_bwd<12>(p, rows, st);
-    return launch_bwd<16>(p, rows, st);
+    return attn_bucket<4, 8, 12, 16>(S, [&](auto nkt) { return launch_bwd<nkt()>(p, rows, c.stream); });
 }

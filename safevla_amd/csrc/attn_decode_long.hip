@@ -12,8 +12,7 @@
 //  * both passes walk only the set bits of that mask, DECL_U blocks per trip with all of a trip's loads issued before the first use: the cost follows the
 //    episode's length, not the window;
 //  * scores wait in LDS (4 KiB) between the passes instead of in registers.
-#include "attn_common.h"      // LOG2E / LN2
-#include "attn_decode_long.h"
+#include "attn_host.h"      // AttnCall, DECL_MAXS; attn_common.h: LOG2E / LN2
 
 #define HD 64
 #define DECL_THREADS 256
@@ -154,9 +153,8 @@ __device__ __forceinline__ void attn_decode_long_kernel_body(DecLongArgs p) {
 }
 __global__ void __launch_bounds__(DECL_THREADS) attn_decode_long_kernel(DecLongArgs p) { attn_decode_long_kernel_body(p); }
 
-int attn_decode_long_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long ld, bf16_t* O, long ldo, float* LSE, int rows, int S, int H, float scale,
-                            const unsigned char* kvalid, long ldq, int kv_rows, void* stream) {
-    if (rows <= 0 || S <= 0 || S > DECL_MAXS || (ld % 8) || (ldq % 8) || H <= 0 || kv_rows < S) return SVLA_EINVAL;
-    DecLongArgs p{Q, K, V, ld, O, ldo, LSE, kvalid, S, H, scale, kv_rows, ldq};
-    return SVLA_LAUNCH(attn_decode_long_kernel, attn_decode_long_kernel_body, DECL_THREADS, 1, dim3(rows * H), dim3(DECL_THREADS), 0, (hipStream_t)stream, p);
+int attn_decode_long_launch(const AttnCall& c) {
+    if (!attn_accepts(c, ATTN_FWD_64_DECODE_L)) return SVLA_EINVAL;
+    DecLongArgs p{c.Q, c.K, c.V, c.ld, c.O, c.ldo, c.LSE, c.kvalid, c.S, c.H, c.scale, attn_kv_rows(c), c.ldq};
+    return SVLA_LAUNCH(attn_decode_long_kernel, attn_decode_long_kernel_body, DECL_THREADS, 1, dim3(c.rows * c.H), dim3(DECL_THREADS), 0, c.stream, p);
 }

@@ -26,8 +26,7 @@
 //  * staging stores (ds_write_b128, 8 lanes = two whole rows = 128 contiguous bytes): any fB.
 // fB = 0,2,3,1 satisfies all three (1 ^ fB(1) = 3, 1 ^ fB(2) = 2); both panels are conflict-free for both kinds of read under the
 // bank rule above.
-#include "attn_common.h"      // dropout index, panel A's swizzle (att_swz), fragment helpers
-#include "attn_hd96.h"
+#include "attn_host.h"      // AttnCall; attn_common.h: dropout index, panel A's swizzle (att_swz), fragment helpers
 
 #define HD96 96
 #define A96_THREADS 256
@@ -498,39 +497,16 @@ static int a96_launch_bwd(const Attn96Args& p, int rows, hipStream_t st) {
                    : svla_launch<attn96_bwd_dkv_kernel<NKT, false>>(grid, block, lds_kv, st, p);
 }
 
-int attn96_fwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long ld, bf16_t* O, long ldo, float* LSE, int rows, int S, int H,
-                      float scale, int mask_mode, const int* traj, const float* bias, const unsigned char* kvalid, int Sq, long ldq, int kv_rows,
-                      const svla_dropout* drop, void* stream) {
-    if (rows <= 0 || S <= 0 || S > 256 || bias || (ld % 8) || (ldo % 4) || H <= 0 || (kv_rows > 0 && kv_rows < S)) return SVLA_EINVAL;
-    if (mask_mode != MASK_NONE && (mask_mode != MASK_BLOCK_CAUSAL || !traj)) return SVLA_EINVAL;
-    if (Sq < 0 || Sq > S || (Sq > 0 && (ldq % 8))) return SVLA_EINVAL;
-    Attn96Args p{};
-    p.Q = Q; p.K = K; p.V = V; p.ld = ld; p.O = O; p.ldo = ldo; p.LSE = LSE; p.traj = traj; p.kvalid = kvalid;
-    p.S = S; p.H = H; p.mask_mode = mask_mode; p.scale = scale;
-    p.Sq = Sq > 0 ? Sq : S; p.ldq = Sq > 0 ? ldq : ld;
-    p.kv_rows = kv_rows > 0 ? kv_rows : S;
-    p.drop = drop_cfg(drop);
-    hipStream_t st = (hipStream_t)stream;
-    if (S <= 64) return a96_launch_fwd<4>(p, rows, st);
-    if (S <= 128) return a96_launch_fwd<8>(p, rows, st);
-    if (S <= 192) return a96_launch_fwd<12>(p, rows, st);
-    return a96_launch_fwd<16>(p, rows, st);
+int attn96_fwd_launch(const AttnCall& c) {
+    if (!attn_accepts(c, ATTN_FWD_96)) return SVLA_EINVAL;
+    Attn96Args p = attn_fill<Attn96Args>(c);
+    p.kv_rows = attn_kv_rows(c);
+    return attn_bucket<4, 8, 12, 16>(c.S, [&](auto nkt) { return a96_launch_fwd<nkt()>(p, c.rows, c.stream); });
 }
 
-int attn96_bwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long ld, const bf16_t* O, long ldo, const float* LSE, const bf16_t* dO,
-                      long lddo, bf16_t* dQ, bf16_t* dK, bf16_t* dV, long ldd, int rows, int S, int H, float scale, int mask_mode, const int* traj,
-                      const float* bias, const unsigned char* kvalid, int Sq, long ldq, long lddq, float* D_ws, const svla_dropout* drop, void* stream) {
-    if (rows <= 0 || S <= 0 || S > 256 || bias || (ld % 8) || (ldo % 8) || (lddo % 8) || (ldd % 4) || H <= 0) return SVLA_EINVAL;
-    if (mask_mode != MASK_NONE && (mask_mode != MASK_BLOCK_CAUSAL || !traj)) return SVLA_EINVAL;
-    if (Sq < 0 || Sq > S || (Sq > 0 && ((ldq % 8) || (lddq % 4)))) return SVLA_EINVAL;
-    Attn96Args p{};
-    p.Sq = Sq > 0 ? Sq : S; p.ldq = Sq > 0 ? ldq : ld; p.lddq = Sq > 0 ? lddq : ldd; p.kv_rows = S;
-    p.Q = Q; p.K = K; p.V = V; p.ld = ld; p.O = (bf16_t*)O; p.ldo = ldo; p.LSE = (float*)LSE; p.dO = dO; p.lddo = lddo;
-    p.dQ = dQ; p.dK = dK; p.dV = dV; p.ldd = ldd; p.traj = traj; p.kvalid = kvalid;
-    p.S = S; p.H = H; p.mask_mode = mask_mode; p.scale = scale; p.Dws = D_ws; p.drop = drop_cfg(drop);
-    hipStream_t st = (hipStream_t)stream;
-    if (S <= 64) return a96_launch_bwd<4>(p, rows, st);
-    if (S <= 128) return a96_launch_bwd<8>(p, rows, st);
-    if (S <= 192) return a96_launch_bwd<12>(p, rows, st);
-    return a96_launch_bwd<16>(p, rows, st);
+int attn96_bwd_launch(const AttnCall& c) {
+    if (!attn_accepts(c, ATTN_BWD_96)) return SVLA_EINVAL;
+    Attn96Args p = attn_fill<Attn96Args>(c);
+    p.kv_rows = c.S; p.Dws = c.D_ws;
+    return attn_bucket<4, 8, 12, 16>(c.S, [&](auto nkt) { return a96_launch_bwd<nkt()>(p, c.rows, c.stream); });
 }

@@ -15,8 +15,7 @@
 //   * with the block-causal mask the tile pairs that lie wholly above the diagonal are skipped (wave-uniform loop bounds): half the work of a decoder layer;
 //   * the next tile's Q / dO (K / V) fragments are fetched from global memory while the current tile is computed.
 // Not built here: the T5 bias (the only biased attention is frozen and has no backward), S > 512, head_dim 96.
-#include "attn_common.h"      // dropout index, LDS swizzle (att_swz) and lane bases, fragment helpers
-#include "attn_long.h"
+#include "attn_host.h"      // AttnCall; attn_common.h: dropout index, LDS swizzle (att_swz) and lane bases, fragment helpers
 
 #define AL_HD 64
 #define AL_ROW LDSROW       // LDS row = 128 B, 16-byte chunks XOR-swizzled (att_swz)
@@ -287,25 +286,14 @@ __global__ void __launch_bounds__(AL_THREADS) attn_long_bwd_dkv_kernel(AttnLongA
 }
 
 // ================================================================================================ launcher
-int attn_long_bwd_launch(const bf16_t* Q, const bf16_t* K, const bf16_t* V, long ld, const bf16_t* O, long ldo, const float* LSE, const bf16_t* dO,
-                         long lddo, bf16_t* dQ, bf16_t* dK, bf16_t* dV, long ldd, int rows, int S, int H, float scale, int mask_mode, const int* traj,
-                         const float* bias, const unsigned char* kvalid, int Sq, long ldq, long lddq, float* D_ws, const svla_dropout* drop, void* stream) {
-    (void)D_ws;      // the dK/dV kernel computes D itself (O is read once per (row, head) either way); accepted so that callers need not know the bucket
-    if (rows <= 0 || S <= 256 || S > 512 || (ld % 8) || (lddo % 8) || (ldo % 8) || (ldd % 4) || H <= 0 || bias) return SVLA_EINVAL;
-    if (mask_mode != MASK_NONE && mask_mode != MASK_BLOCK_CAUSAL) return SVLA_EINVAL;
-    if (mask_mode == MASK_BLOCK_CAUSAL && !traj) return SVLA_EINVAL;
-    if (Sq < 0 || Sq > S || (Sq > 0 && ((ldq % 8) || (lddq % 4)))) return SVLA_EINVAL;
-    AttnLongArgs p{};
-    p.Sq = Sq > 0 ? Sq : S; p.ldq = Sq > 0 ? ldq : ld; p.lddq = Sq > 0 ? lddq : ldd;
-    p.Q = Q; p.K = K; p.V = V; p.ld = ld; p.O = O; p.ldo = ldo; p.LSE = LSE; p.dO = dO; p.lddo = lddo;
-    p.dQ = dQ; p.dK = dK; p.dV = dV; p.ldd = ldd; p.traj = traj; p.kvalid = kvalid;
-    p.S = S; p.H = H; p.mask_mode = mask_mode; p.scale = scale; p.drop = drop_cfg(drop);
-    const int SP = (S + 31) & ~31;      // the LDS image grows with S: the opt-in follows the largest window seen
-    hipStream_t st = (hipStream_t)stream;
-    const dim3 grid(rows * H), block(AL_THREADS);
-    const bool generic = mask_mode != MASK_NONE || kvalid;
-    if (const int rc = generic ? svla_launch<attn_long_bwd_dq_kernel<true>>(grid, block, al_lds_dq(SP), st, p)
-                               : svla_launch<attn_long_bwd_dq_kernel<false>>(grid, block, al_lds_dq(SP), st, p)) return rc;
-    return generic ? svla_launch<attn_long_bwd_dkv_kernel<true>>(grid, block, al_lds_dkv(SP), st, p)
-                   : svla_launch<attn_long_bwd_dkv_kernel<false>>(grid, block, al_lds_dkv(SP), st, p);
+int attn_long_bwd_launch(const AttnCall& c) {
+    if (!attn_accepts(c, ATTN_BWD_64_LONG)) return SVLA_EINVAL;
+    const AttnLongArgs p = attn_fill<AttnLongArgs>(c);
+    const int SP = (c.S + 31) & ~31;      // the LDS image grows with S: the opt-in follows the largest window seen
+    const dim3 grid(c.rows * c.H), block(AL_THREADS);
+    const bool generic = c.mask_mode != MASK_NONE || c.kvalid;
+    if (const int rc = generic ? svla_launch<attn_long_bwd_dq_kernel<true>>(grid, block, al_lds_dq(SP), c.stream, p)
+                               : svla_launch<attn_long_bwd_dq_kernel<false>>(grid, block, al_lds_dq(SP), c.stream, p)) return rc;
+    return generic ? svla_launch<attn_long_bwd_dkv_kernel<true>>(grid, block, al_lds_dkv(SP), c.stream, p)
+                   : svla_launch<attn_long_bwd_dkv_kernel<false>>(grid, block, al_lds_dkv(SP), c.stream, p);
 }
