@@ -209,7 +209,8 @@ int svla_replay_calls(int n, const int* fn_ids, const int* arg_offsets, const un
  * (training/online/allenact_trainer.py via AllenAct's collect_step; forward at allenact_dino_transformer.py:326-475): DINO tokens (tok_bytes of bf16 [B, 2, 84, C]), previous
  * actions [B], masks [B], object-in-hand [B], time step [B], goal token ids [B, L] -> their static copies, the T5 padding mask as int64 and uint8 ((id != 0), column 0 always on),
  * the KV-cache window mask kvalid[b, s] = (s <= t) & (s >= max(t - time_step[b], 0)) for s < max_steps (:388-397), the device-resident step counter t_dev = t, and
- * seed_k += seed_inc (mod 2^32) for the up to three device-resident dropout seeds (NULL: skipped). */
+ * seed_k += seed_inc (mod 2^32) for the up to three device-resident dropout seeds (NULL: skipped).  hand_src == hand_dst == NULL: a model without the in-hand sensor
+ * (navigation-only towers); everything else is staged as before.  One of the two NULL: SVLA_EINVAL. */
 int svla_acting_stage(const void* tok_src, void* tok_dst, long tok_bytes, const int64_t* pa_src, int64_t* pa_dst, const float* mask_src, float* mask_dst,
                       const int64_t* hand_src, int64_t* hand_dst, const int64_t* ts_src, int64_t* ts_dst, const int64_t* ids_src, int64_t* ids_dst, int64_t* am_dst,
                       unsigned char* am8_dst, unsigned char* kvalid_dst, int64_t* t_dev, int B, int L, int max_steps, int t, int* seed0, int* seed1, int* seed2,
@@ -289,7 +290,10 @@ int svla_fusion_fill(const float* fusion_token, const svla_bf16* text, const int
 int svla_fusion_text_bwd(const svla_bf16* dx0, const int* gid, int T, int B, int S, int L, int text_off, int D, float* dtext,
                          void* stream);
 /* prev-action (null token where masks == 0) + in-hand embeddings + sinusoidal time encoding
- * (allenact_dino_transformer.py:353-385; architecture/models/transformer_models/text_cond_visual_encoder.py:263-283). */
+ * (allenact_dino_transformer.py:353-385; architecture/models/transformer_models/text_cond_visual_encoder.py:263-283).
+ * Sensor subsets (the reference builds either embedding only with its sensor, text_cond_visual_encoder.py:101-111): an absent term is passed as NULL and skipped --
+ * hand_tab (d_hand_tab) == NULL && hand == NULL: no in-hand term; act_tab (d_act_tab) == NULL && prev_actions == NULL && masks == NULL: no previous-action term.  The
+ * remaining additions keep their order.  A group with some members NULL and others not returns SVLA_EINVAL and launches nothing.  The same holds for the _f32 twins. */
 int svla_decoder_embed_fwd(const svla_bf16* xf, long xf_row_stride, const float* act_tab, const float* hand_tab,
                            const float* div_term, const int64_t* prev_actions, const float* masks, const int64_t* hand,
                            const int64_t* time_step, int T, int B, int n_actions, int D, svla_bf16* out, void* stream);

@@ -30,6 +30,8 @@ STRETCH_LONG_NAMES = {"m": "move_ahead", "r": "rotate_right", "l": "rotate_left"
                       "zm": "move_arm_in", "zp": "move_arm_out", "yp": "move_arm_up", "ym": "move_arm_down", "wp": "wrist_open",
                       "wm": "wrist_close", "yms": "move_arm_down_small", "zms": "move_arm_in_small", "zps": "move_arm_out_small",
                       "yps": "move_arm_up_small", "d": "dropoff"}
+# what a navigation-only policy may choose (dinov2_vits_tsfm_base.py:272-289): move_ahead, rotate_right, rotate_left, move_back, done, rotate_right_small, rotate_left_small
+NAV_ACTIONS = ("m", "r", "l", "b", "end", "rs", "ls")
 
 
 class AbstractAgent:
@@ -53,8 +55,9 @@ class InferenceAgentVIDA(AbstractAgent):
         self.greedy_sampling = greedy_sampling
         u = actor_critic.uuids
         self.nav_pre = nav_preprocessor or DinoViTPreprocessor("rgb_raw", u["nav"], device=device)
-        self.manip_pre = manip_preprocessor or DinoViTPreprocessor("manipulation_rgb_raw", u["manip"], device=device)
-        if manip_preprocessor is None and nav_preprocessor is None:
+        # a policy without the manipulation camera (manipulation_rgb_dino_preprocessor_uuid=None) gets no preprocessor for it
+        self.manip_pre = None if u["manip"] is None else (manip_preprocessor or DinoViTPreprocessor("manipulation_rgb_raw", u["manip"], device=device))
+        if self.manip_pre is not None and manip_preprocessor is None and nav_preprocessor is None:
             self.manip_pre.vit = self.nav_pre.vit            # one frozen ViT serves both cameras
         self.steps_before_rollout_refresh = steps_before_rollout_refresh
         self.rollout_storage = RolloutStorage(steps_before_rollout_refresh, device=device, store_tokens=True,
@@ -105,7 +108,7 @@ class InferenceAgentVIDA(AbstractAgent):
             if missing:
                 warnings.warn(f"DINOv2 weights: {len(missing)} tensors not found (e.g. {missing[:3]}); those stay random-init")
             agent.nav_pre.vit.sync()
-            if agent.manip_pre.vit is not agent.nav_pre.vit:
+            if agent.manip_pre is not None and agent.manip_pre.vit is not agent.nav_pre.vit:
                 agent.manip_pre.vit.load_state_dict(vit_sd, strict=False)
                 agent.manip_pre.vit.sync()
         if ckpt_path is not None:
@@ -149,15 +152,18 @@ class InferenceAgentVIDA(AbstractAgent):
         dev, u = self.device, self.actor_critic.uuids
         as_u8 = lambda a: torch.as_tensor(np.ascontiguousarray(a)).to(dev).reshape((1,) + tuple(np.shape(a)))
         nav = as_u8(observations["rgb_raw"])
-        manip = as_u8(observations["manipulation_rgb_raw"]) if "manipulation_rgb_raw" in observations else torch.zeros_like(nav)
-        return {
+        batch = {
             u["nav"]: self.nav_pre.process({"rgb_raw": nav}),
-            u["manip"]: self.manip_pre.process({"manipulation_rgb_raw": manip}),
             u["goal"]: torch.as_tensor(np.asarray(observations["natural_language_spec"], dtype=np.uint8)).to(dev).reshape(1, -1),
             u["time"]: torch.tensor([int(observations["time_step"])], device=dev, dtype=torch.int64),
             u["traj"]: torch.tensor([int(observations["traj_index"])], device=dev, dtype=torch.int64),
-            u["hand"]: torch.tensor([int(np.asarray(observations.get("an_object_is_in_hand", 0)).reshape(-1)[0])], device=dev, dtype=torch.int64),
         }
+        if self.manip_pre is not None:
+            manip = as_u8(observations["manipulation_rgb_raw"]) if "manipulation_rgb_raw" in observations else torch.zeros_like(nav)
+            batch[u["manip"]] = self.manip_pre.process({"manipulation_rgb_raw": manip})
+        if u["hand"] is not None:      # a policy without the in-hand sensor reads no such observation
+            batch[u["hand"]] = torch.tensor([int(np.asarray(observations.get("an_object_is_in_hand", 0)).reshape(-1)[0])], device=dev, dtype=torch.int64)
+        return batch
 
     def _remember(self, obs_batch: Dict[str, torch.Tensor]):
         """Feed the step's observations to the rollout storage the way the update path's storage is fed: a task's first step

@@ -430,19 +430,26 @@ __global__ void decoder_embed_f32_kernel(const float* __restrict__ xf, long xf_r
                                          int D, float* __restrict__ out) {
     const int row = blockIdx.x;            // (t*B + b)
     const int t = row / B, b = row % B;
-    const int64_t a = masks[row] != 0.f ? prev_actions[row] : (int64_t)n_actions;
+    // act_tab == NULL / hand_tab == NULL: a model without that embedding (csrc/misc.hip: decoder_embed); uniform over the grid
+    const float* at_row = act_tab ? act_tab + (size_t)(masks[row] != 0.f ? prev_actions[row] : (int64_t)n_actions) * D : nullptr;
+    const float* ht_row = hand_tab ? hand_tab + (size_t)hand[row] * D : nullptr;
     const float pos = (float)time_step[row];
     for (int c = threadIdx.x; c < D; c += blockDim.x) {
         const float ang = pos * div_term[c >> 1];
         const float pe = (c & 1) ? cosf(ang) : sinf(ang);
         // reference order: time_enc + ((obs + prev_action_emb) + in_hand_emb)
-        out[((size_t)b * T + t) * D + c] = pe + ((xf[(size_t)row * xf_row_stride + c] + act_tab[(size_t)a * D + c]) + hand_tab[(size_t)hand[row] * D + c]);
+        float v = xf[(size_t)row * xf_row_stride + c];
+        if (at_row) v = v + at_row[c];
+        if (ht_row) v = v + ht_row[c];
+        out[((size_t)b * T + t) * D + c] = pe + v;
     }
 }
 extern "C" int svla_decoder_embed_fwd_f32(const float* xf, long xf_row_stride, const float* act_tab, const float* hand_tab,
                                           const float* div_term, const int64_t* prev_actions, const float* masks, const int64_t* hand,
                                           const int64_t* time_step, int T, int B, int n_actions, int D, float* out, void* stream) {
     if (T <= 0 || B <= 0 || D <= 0) return SVLA_EINVAL;
+    if ((hand_tab == nullptr) != (hand == nullptr)) return SVLA_EINVAL;
+    if ((act_tab == nullptr) != (prev_actions == nullptr) || (act_tab == nullptr) != (masks == nullptr)) return SVLA_EINVAL;
     hipLaunchKernelGGL(decoder_embed_f32_kernel, dim3(T * B), dim3(256), 0, (hipStream_t)stream, xf, xf_row_stride, act_tab, hand_tab, div_term,
                        prev_actions, masks, hand, time_step, T, B, n_actions, D, out);
     return svla_launch_status();
@@ -454,19 +461,21 @@ __global__ void decoder_embed_bwd_f32_kernel(const float* __restrict__ dout, con
                                              float* __restrict__ d_hand_tab) {
     const int row = blockIdx.x;
     const int t = row / B, b = row % B;
-    const int a = masks[row] != 0.f ? (int)prev_actions[row] : n_actions;
-    const int hh = (int)hand[row];
+    const int a = d_act_tab ? (masks[row] != 0.f ? (int)prev_actions[row] : n_actions) : 0;
+    const int hh = d_hand_tab ? (int)hand[row] : 0;
     for (int c = threadIdx.x; c < D; c += blockDim.x) {
         const float v = dout[((size_t)b * T + t) * D + c];
         dxf[(size_t)row * dxf_row_stride + c] = v;
-        atomicAdd(d_act_tab + (size_t)a * D + c, v);
-        atomicAdd(d_hand_tab + (size_t)hh * D + c, v);
+        if (d_act_tab) atomicAdd(d_act_tab + (size_t)a * D + c, v);
+        if (d_hand_tab) atomicAdd(d_hand_tab + (size_t)hh * D + c, v);
     }
 }
 extern "C" int svla_decoder_embed_bwd_f32(const float* dout, const int64_t* prev_actions, const float* masks, const int64_t* hand, int T,
                                           int B, int n_actions, int D, float* dxf, long dxf_row_stride, float* d_act_tab, float* d_hand_tab,
                                           void* stream) {
     if (T <= 0 || B <= 0 || D <= 0) return SVLA_EINVAL;
+    if ((d_hand_tab == nullptr) != (hand == nullptr)) return SVLA_EINVAL;
+    if ((d_act_tab == nullptr) != (prev_actions == nullptr) || (d_act_tab == nullptr) != (masks == nullptr)) return SVLA_EINVAL;
     hipLaunchKernelGGL(decoder_embed_bwd_f32_kernel, dim3(T * B), dim3(256), 0, (hipStream_t)stream, dout, prev_actions, masks, hand, T, B,
                        n_actions, D, dxf, dxf_row_stride, d_act_tab, d_hand_tab);
     return svla_launch_status();

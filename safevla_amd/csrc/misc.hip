@@ -94,6 +94,9 @@ extern "C" int svla_fusion_text_bwd(const bf16_t* dx0, const int* gid, int T, in
 // Decoder input (allenact_dino_transformer.py:353-385 + text_cond_visual_encoder.py:263-283):
 //   out[b*T + t, :] = xf[(t*B+b)*S*512 + :]  (fusion token output)  + act_tab[masks ? prev_action : A] + hand_tab[hand]
 //                   + pe(time_step),  pe[2i] = sin(pos*div[i]), pe[2i+1] = cos(pos*div[i])
+// Sensor subsets: a model without the previous-action embedding passes act_tab = prev_actions = masks = NULL, one without the in-hand sensor hand_tab = hand = NULL
+// (text_cond_visual_encoder.py:101-111 builds either embedding only with its sensor).  The term is then skipped and the remaining additions keep their order.  The
+// pointers are kernel arguments: both branches are uniform over the grid, so no wave diverges on them.
 __device__ __forceinline__ void decoder_embed_kernel_body(const bf16_t* __restrict__ xf, long xf_row_stride, const float* __restrict__ act_tab,
                                      const float* __restrict__ hand_tab, const float* __restrict__ div_term,
                                      const int64_t* __restrict__ prev_actions, const float* __restrict__ masks,
@@ -102,19 +105,28 @@ __device__ __forceinline__ void decoder_embed_kernel_body(const bf16_t* __restri
     const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63;
     if (wave >= T * B) return;
     const int t = wave / B, b = wave % B;
-    const int64_t a = masks[wave] != 0.f ? prev_actions[wave] : (int64_t)n_actions;
+    const float* at_row = act_tab ? act_tab + (size_t)(masks[wave] != 0.f ? prev_actions[wave] : (int64_t)n_actions) * D : nullptr;
+    const float* ht_row = hand_tab ? hand_tab + (size_t)hand[wave] * D : nullptr;
     const float pos = (float)time_step[wave];
     for (int c = lane * 8; c < D; c += 512) {       // D = 512: one trip
         const u32x4 w = *(const u32x4*)(xf + (size_t)wave * xf_row_stride + c);
-        const float* at = act_tab + (size_t)a * D + c;
-        const float* ht = hand_tab + (size_t)hand[wave] * D + c;
         float v[8];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { v[2 * e] = bf_lo(w[e]); v[2 * e + 1] = bf_hi(w[e]); }
+        // reference order: time_enc + ((obs + prev_action_emb) + in_hand_emb)
+        if (at_row) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = v[e] + at_row[c + e];
+        }
+        if (ht_row) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) v[e] = v[e] + ht_row[c + e];
+        }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float ang = pos * div_term[c / 2 + e];
-            // reference order: time_enc + ((obs + prev_action_emb) + in_hand_emb)
-            v[2 * e] = sinf(ang) + ((bf_lo(w[e]) + at[2 * e]) + ht[2 * e]);
-            v[2 * e + 1] = cosf(ang) + ((bf_hi(w[e]) + at[2 * e + 1]) + ht[2 * e + 1]);
+            v[2 * e] = sinf(ang) + v[2 * e];
+            v[2 * e + 1] = cosf(ang) + v[2 * e + 1];
         }
         u32x4 o;
 #pragma unroll
@@ -133,21 +145,26 @@ extern "C" int svla_decoder_embed_fwd(const bf16_t* xf, long xf_row_stride, cons
                                       const int64_t* hand, const int64_t* time_step, int T, int B, int n_actions, int D, bf16_t* out,
                                       void* stream) {
     if (T <= 0 || B <= 0 || D <= 0 || (D % 8)) return SVLA_EINVAL;
+    if ((hand_tab == nullptr) != (hand == nullptr)) return SVLA_EINVAL;                                       // a table without its indices, or the reverse
+    if ((act_tab == nullptr) != (prev_actions == nullptr) || (act_tab == nullptr) != (masks == nullptr)) return SVLA_EINVAL;
     return SVLA_LAUNCH(decoder_embed_kernel, decoder_embed_kernel_body, 1024, 1, dim3((T * B + 3) / 4), dim3(256), 0, (hipStream_t)stream, xf, xf_row_stride, act_tab,
                        hand_tab, div_term, prev_actions, masks, hand, time_step, T, B, n_actions, D, out);
 }
 
 // dxf[(t*B+b) row, :] = dout[b*T+t, :];  d act_tab / d hand_tab accumulated in LDS per block, then flushed.
 // DET: the per-block LDS table is fixed-point too (the four waves of a block reach it in arbitrary order).
+// Sensor subsets (see the forward): d_act_tab = prev_actions = masks = NULL and / or d_hand_tab = hand = NULL.  The LDS table holds the rows of the tables present
+// only -- action rows first, ``hand_base`` = where the in-hand rows start -- and with neither table the kernel is the row copy alone (no LDS).
 template <bool DET>
 __global__ void decoder_embed_bwd_kernel(const bf16_t* __restrict__ dout, const int64_t* __restrict__ prev_actions,
                                          const float* __restrict__ masks, const int64_t* __restrict__ hand, int T, int B,
                                          int n_actions, int D, bf16_t* __restrict__ dxf, long dxf_row_stride,
                                          float* __restrict__ d_act_tab, float* __restrict__ d_hand_tab, DetCfg det) {
-    extern __shared__ __attribute__((aligned(16))) char tab_raw[];  // [(n_actions + 2) + 3][D] float (or 64-bit fixed point)
+    extern __shared__ __attribute__((aligned(16))) char tab_raw[];  // [(n_actions + 2 if d_act_tab) + (3 if d_hand_tab)][D] float (or 64-bit fixed point)
     typedef typename std::conditional<DET, unsigned long long, float>::type acc_t;
     acc_t* tab = (acc_t*)tab_raw;
-    const int nrows_tab = n_actions + 2 + 3;
+    const int hand_base = d_act_tab ? n_actions + 2 : 0;
+    const int nrows_tab = hand_base + (d_hand_tab ? 3 : 0);
     for (int i = threadIdx.x; i < nrows_tab * D; i += blockDim.x) tab[i] = (acc_t)0;
     __syncthreads();
     const int lane = threadIdx.x & 63;
@@ -156,25 +173,29 @@ __global__ void decoder_embed_bwd_kernel(const bf16_t* __restrict__ dout, const 
         if constexpr (DET) {
             if (fabsf(v) < det.max_partial) atomicAdd(&tab[idx], det_fixed(det, v));      // < 8192 rows per block: the table cannot wrap
             else {      // NaN / Inf / huge: straight to fp32, visible -- and counted (svla_det_bypass_count)
-                atomicAdd(idx < (n_actions + 2) * D ? &d_act_tab[idx] : &d_hand_tab[idx - (n_actions + 2) * D], v);
+                atomicAdd(idx < hand_base * D ? &d_act_tab[idx] : &d_hand_tab[idx - hand_base * D], v);
                 if (det.bypass) atomicAdd(det.bypass, 1ull);
             }
         } else atomicAdd(&tab[idx], v);
     };
     for (int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6; wave < T * B; wave += nw) {
         const int t = wave / B, b = wave % B;
-        const int a = masks[wave] != 0.f ? (int)prev_actions[wave] : n_actions;
-        const int hh = n_actions + 2 + (int)hand[wave];
+        const int a = d_act_tab ? (masks[wave] != 0.f ? (int)prev_actions[wave] : n_actions) : 0;
+        const int hh = d_hand_tab ? hand_base + (int)hand[wave] : 0;
         for (int c = lane * 8; c < D; c += 512) {       // D = 512: one trip
             const u32x4 w = *(const u32x4*)(dout + ((size_t)b * T + t) * D + c);
             *(u32x4*)(dxf + (size_t)wave * dxf_row_stride + c) = w;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float lo = bf_lo(w[e]), hi = bf_hi(w[e]);
-                add(a * D + c + 2 * e, lo);
-                add(a * D + c + 2 * e + 1, hi);
-                add(hh * D + c + 2 * e, lo);
-                add(hh * D + c + 2 * e + 1, hi);
+                if (d_act_tab) {
+                    add(a * D + c + 2 * e, lo);
+                    add(a * D + c + 2 * e + 1, hi);
+                }
+                if (d_hand_tab) {
+                    add(hh * D + c + 2 * e, lo);
+                    add(hh * D + c + 2 * e + 1, hi);
+                }
             }
         }
     }
@@ -183,8 +204,8 @@ __global__ void decoder_embed_bwd_kernel(const bf16_t* __restrict__ dout, const 
         float v;
         if constexpr (DET) v = (float)((double)(long long)tab[i] * det.unscale); else v = tab[i];
         if (v != 0.f) {
-            if (i < (n_actions + 2) * D) grad_add(det, &d_act_tab[i], v);
-            else grad_add(det, &d_hand_tab[i - (n_actions + 2) * D], v);
+            if (i < hand_base * D) grad_add(det, &d_act_tab[i], v);
+            else grad_add(det, &d_hand_tab[i - hand_base * D], v);
         }
     }
 }
@@ -193,8 +214,10 @@ extern "C" int svla_decoder_embed_bwd(const bf16_t* dout, const int64_t* prev_ac
                                       int T, int B, int n_actions, int D, bf16_t* dxf, long dxf_row_stride, float* d_act_tab,
                                       float* d_hand_tab, void* stream) {
     if (T <= 0 || B <= 0 || D <= 0 || (D % 8)) return SVLA_EINVAL;
+    if ((d_hand_tab == nullptr) != (hand == nullptr)) return SVLA_EINVAL;
+    if ((d_act_tab == nullptr) != (prev_actions == nullptr) || (d_act_tab == nullptr) != (masks == nullptr)) return SVLA_EINVAL;
     const bool det = g_svla_det.i64[0] != nullptr || g_svla_det.i64[1] != nullptr;
-    const size_t lds = (size_t)(n_actions + 5) * D * (det ? sizeof(unsigned long long) : sizeof(float));
+    const size_t lds = (size_t)((d_act_tab ? n_actions + 2 : 0) + (d_hand_tab ? 3 : 0)) * D * (det ? sizeof(unsigned long long) : sizeof(float));
     if (lds > 160 * 1024) return SVLA_EINVAL;
     int blocks = (T * B + 63) / 64;
     if (blocks > 128) blocks = 128;
@@ -725,7 +748,8 @@ __global__ void acting_stage_kernel(ActingStageArgs a) {
     const int b = bid - a.nb_tok;
     const long ts = a.ts_src[b];
     if (threadIdx.x == 0) {
-        a.pa_dst[b] = a.pa_src[b]; a.mask_dst[b] = a.mask_src[b]; a.hand_dst[b] = a.hand_src[b]; a.ts_dst[b] = ts;
+        a.pa_dst[b] = a.pa_src[b]; a.mask_dst[b] = a.mask_src[b]; a.ts_dst[b] = ts;
+        if (a.hand_src) a.hand_dst[b] = a.hand_src[b];       // NULL pair: a model without the in-hand sensor
         if (b == 0) {
             *a.t_dev = (int64_t)a.t;
 #pragma unroll
@@ -745,7 +769,8 @@ extern "C" int svla_acting_stage(const void* tok_src, void* tok_dst, long tok_by
                                  int64_t* am_dst, unsigned char* am8_dst, unsigned char* kvalid_dst, int64_t* t_dev, int B, int L, int max_steps, int t,
                                  int* seed0, int* seed1, int* seed2, int seed_inc, void* stream) {
     if (B <= 0 || L <= 0 || max_steps <= 0 || t < 0 || tok_bytes <= 0 || (tok_bytes % 16) || ((uintptr_t)tok_src % 16) || ((uintptr_t)tok_dst % 16)) return SVLA_EINVAL;
-    if (!pa_src || !pa_dst || !mask_src || !mask_dst || !hand_src || !hand_dst || !ts_src || !ts_dst || !ids_src || !ids_dst || !am_dst || !am8_dst || !kvalid_dst || !t_dev) return SVLA_EINVAL;
+    if ((hand_src == nullptr) != (hand_dst == nullptr)) return SVLA_EINVAL;
+    if (!pa_src || !pa_dst || !mask_src || !mask_dst || !ts_src || !ts_dst || !ids_src || !ids_dst || !am_dst || !am8_dst || !kvalid_dst || !t_dev) return SVLA_EINVAL;
     ActingStageArgs a;
     a.tok_src = (const u32x4*)tok_src; a.tok_dst = (u32x4*)tok_dst; a.n_tok16 = tok_bytes / 16;
     long nb = (a.n_tok16 + 1023) / 1024; if (nb > 512) nb = 512; if (nb < 1) nb = 1;

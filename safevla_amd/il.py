@@ -20,9 +20,9 @@ import numpy as np
 import torch
 
 from . import ops
-from .model import BF16, DINO, F32, N_ACTIONS, NPATCH, TEXT_OFF, Prep, Tower, _Arena, _TowerFn
+from .model import BF16, CAMERAS, DINO, F32, N_ACTIONS, NPATCH, Prep, Tower, _Arena, _TowerFn, sensor_set
 
-NAV, MANIP = "raw_navigation_camera", "raw_manipulation_camera"
+NAV, MANIP = CAMERAS
 START_TOKEN, PAD_TOKEN = N_ACTIONS, N_ACTIONS + 1      # last_actions vocabulary (:95-101)
 
 
@@ -69,8 +69,12 @@ class EarlyFusionCnnTransformer(Tower):
         ops.lib()
         arena = _Arena()
         device = torch.device(device)
+        # ``input_sensors`` decides what is built, as in the reference (early_fusion_tsfm_models.py:90-102, text_cond_visual_encoder.py:101-111): a camera token per
+        # listed camera, ``last_actions_embed`` only with "last_actions", ``object_in_hand_embed`` only with "an_object_is_in_hand"; unknown names are a ValueError
+        cameras, in_hand, prev_actions = sensor_set(input_sensors)
         super().__init__(arena, device, n_fusion_layers=n_fusion_layers, n_decoder_layers=n_decoder_layers, max_steps=max_length, dino_dim=dino_dim,
-                         text_encoder=text_encoder, d_model=d_model, n_heads=n_heads, n_heads_decoder=n_heads_decoder)
+                         text_encoder=text_encoder, d_model=d_model, n_heads=n_heads, n_heads_decoder=n_heads_decoder, cameras=cameras, in_hand=in_hand,
+                         prev_actions=prev_actions)
         arena.build(device)
         self.bind()
         self.towers = [self]
@@ -83,7 +87,7 @@ class EarlyFusionCnnTransformer(Tower):
         if self.data_augmentation:
             from .preproc import RandomDataAugmenter
             size = (256, 256) if text_encoder.startswith("SigLIP") else None
-            self.augmenters = [RandomDataAugmenter(size=size), RandomDataAugmenter(size=size)]
+            self.augmenters = [RandomDataAugmenter(size=size) for _ in self.cameras]
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self.sync_weights()
 
@@ -129,14 +133,13 @@ class EarlyFusionCnnTransformer(Tower):
     @torch.no_grad()
     def prepare(self, batch: Dict, augment: bool = False) -> Prep:
         dev = self.device_
-        nav = batch[NAV]
-        B, T = nav.shape[:2]
+        B, T = batch[self.cameras[0]].shape[:2]
         R = T * B
         p = Prep()
         p.T, p.B, p.R = T, B, R
         p.acting = False                                         # forward(batch): whole windows, also when T = 1 (the agent's single steps set it)
-        p.tokens = torch.empty(R, 2, NPATCH, self.dino_dim, device=dev, dtype=BF16)
-        for cam, key in enumerate((NAV, MANIP)):
+        p.tokens = torch.empty(R, self.ncam, NPATCH, self.dino_dim, device=dev, dtype=BF16)
+        for cam, key in enumerate(self.cameras):                 # only the model's sensors are read from the batch
             x = batch[key].to(dev)
             if x.dtype == torch.uint8:                           # raw frames [B,T,H,W,3] -> frozen ViT
                 if self.image_preprocessor is None:
@@ -144,14 +147,17 @@ class EarlyFusionCnnTransformer(Tower):
                 if augment:
                     x = self.augmenters[cam].augment_u8(x)
                 fr = x.transpose(0, 1).reshape(R, *x.shape[2:]).contiguous()
-                self.image_preprocessor.process_tokens(fr, p.tokens, cam)
+                self.image_preprocessor.process_tokens(fr, p.tokens, cam, ncam=self.ncam)
             else:                                                # pre-encoded features [B,T,384,7,12]
-                ops.feat_to_tokens(x.transpose(0, 1).reshape(R, self.dino_dim, NPATCH).contiguous().float(), p.tokens, cam)
+                ops.feat_to_tokens(x.transpose(0, 1).reshape(R, self.dino_dim, NPATCH).contiguous().float(), p.tokens, cam, ncam=self.ncam)
         tb = lambda v: v.to(dev).transpose(0, 1).reshape(R).contiguous()     # [B,T] -> rows (t*B + b)
-        la = tb(batch["last_actions"]).to(torch.int64)
-        p.prev_actions = la
-        p.masks = (la != START_TOKEN).to(F32)                    # start token <=> "no previous action" (mask 0 selects row 20)
-        p.hand = tb(batch["an_object_is_in_hand"]).to(torch.int64) if "an_object_is_in_hand" in batch else torch.zeros(R, device=dev, dtype=torch.int64)
+        p.prev_actions = p.masks = p.hand = None
+        if self.has_prev:
+            la = tb(batch["last_actions"]).to(torch.int64)
+            p.prev_actions = la
+            p.masks = (la != START_TOKEN).to(F32)                # start token <=> "no previous action" (mask 0 selects row 20)
+        if self.has_hand:
+            p.hand = tb(batch["an_object_is_in_hand"]).to(torch.int64) if "an_object_is_in_hand" in batch else torch.zeros(R, device=dev, dtype=torch.int64)
         p.time_step = tb(batch["time_ids"]).to(torch.int64)
         p.traj_bt = torch.arange(B, device=dev, dtype=torch.int32)[:, None].expand(B, T).contiguous()   # one trajectory per row: causal
         goals = batch["goals"]
@@ -164,7 +170,7 @@ class EarlyFusionCnnTransformer(Tower):
             p.attn_mask = torch.ones_like(p.ids)
             p.U, p.L = p.ids.shape[0], self.visual_encoder.text_encoder.out_tokens(p.ids.shape[1])
         p.gid = (torch.arange(R, device=dev) % B).to(torch.int32).contiguous()
-        p.S = TEXT_OFF + p.L
+        p.S = self.text_off + p.L
         return p
 
     def _frozen_image_encoder(self, key, dev):
@@ -174,7 +180,7 @@ class EarlyFusionCnnTransformer(Tower):
         if self.text_encoder_name.startswith("SigLIP"):
             # SigLipPreprocessor of preprocessors.py:319-328: tensor_image_preprocessor(size=(256, 256)) resizes camera-sized frames in front of the trunk (one
             # resizing front per camera; 256 x 256 frames pass through it untouched)
-            resize = [SigLIPDataAugmentationPreprocessor(k, k, device=dev) for k in (NAV, MANIP)]
+            resize = [SigLIPDataAugmentationPreprocessor(k, k, device=dev) for k in self.cameras]
             return SigLIPPreprocessor(key, key, siglip_model_type={768: "ViT-B-16-SigLIP-256", 1024: "ViT-L-16-SigLIP-256"}[self.dino_dim], device=dev, augmenter=resize)
         if self.dino_dim == 2048:
             return ClipResNetPreprocessor(key, key, device=dev)
@@ -323,10 +329,13 @@ class EarlyFusionCnnTransformerAgent:
                 warnings.warn(f"episode longer than the {self.max_seq_len}-step KV-cache window: the window restarts (the reference slides it)")
                 self._warned_window = True
         one = lambda v, dt: torch.as_tensor(np.asarray(v)).to(dev).to(dt).reshape(1, 1)
-        batch = {"goals": self.cache["goal"], "time_ids": one(self.curr_t, torch.int64),      # = curr_t, as early_fusion_tsfm_models.py:480 (not the cache slot)
-                 "last_actions": one(START_TOKEN if self.curr_t == 0 else self.cache["last_actions"], torch.int64),
-                 "an_object_is_in_hand": one(np.asarray(observations.get("an_object_is_in_hand", 0)).reshape(-1)[0], torch.int64)}
-        for key in (NAV, MANIP):
+        batch = {"goals": self.cache["goal"], "time_ids": one(self.curr_t, torch.int64)}      # = curr_t, as early_fusion_tsfm_models.py:480 (not the cache slot)
+        # only the model's sensors are read from ``observations`` (early_fusion_tsfm_models.py:410-443)
+        if m.has_prev:
+            batch["last_actions"] = one(START_TOKEN if self.curr_t == 0 else self.cache["last_actions"], torch.int64)
+        if m.has_hand:
+            batch["an_object_is_in_hand"] = one(np.asarray(observations.get("an_object_is_in_hand", 0)).reshape(-1)[0], torch.int64)
+        for key in m.cameras:
             x = torch.as_tensor(np.ascontiguousarray(observations[key])).to(dev)
             batch[key] = x.reshape((1, 1) + tuple(x.shape))
         prep = m.prepare(batch)
@@ -336,6 +345,7 @@ class EarlyFusionCnnTransformerAgent:
         curr = logits.reshape(-1).float()
         probs = torch.softmax(curr, -1)
         idx = int(torch.argmax(curr)) if self.sampling == "greedy" else int(torch.multinomial(probs, 1, generator=self.generator))
-        self.cache["last_actions"] = idx
+        if m.has_prev:                                 # kept only with that sensor (early_fusion_tsfm_models.py:507-508)
+            self.cache["last_actions"] = idx
         self.curr_t += 1
         return self.action_list[idx], probs

@@ -37,7 +37,9 @@ N_ACTIONS = 20
 D = 512
 DINO = 384
 NPATCH = 84          # 7 x 12 grid per camera
-TEXT_OFF = 1 + 2 * NPATCH
+TEXT_OFF = 1 + 2 * NPATCH        # text offset of the two-camera set; a tower's own is ``Tower.text_off`` = 1 + ncam * NPATCH
+CAMERAS = ("raw_navigation_camera", "raw_manipulation_camera")      # the camera sensors that are built, in the order of their fusion tokens
+NON_VISUAL_SENSORS = ("last_actions", "an_object_is_in_hand")
 MAX_ACTING_WINDOW = 1024          # keys of the single-query attention kernels = longest KV-cache window (max_steps) of the acting step
 TEXT_ENCODER_DIMS = {"t5-small": 512, "SigLIPBase": 768, "SigLIPLarge": 1024}
 BF16, F32 = torch.bfloat16, torch.float32
@@ -129,12 +131,36 @@ def _init_tensor(shape, init, g):
 
 
 # ================================================================================================ one tower
+def sensor_set(input_sensors):
+    """``input_sensors`` of the reference's constructors -> (cameras in fusion order, in-hand sensor?, previous action embedded?).  An unknown name is a ValueError that
+    lists what is built: the bbox sensors, ``relative_arm_location_metadata`` and the duplicate cameras of utils/sensor_constant_utils.py are not."""
+    names = list(input_sensors)
+    unknown = [n for n in names if n not in CAMERAS + NON_VISUAL_SENSORS]
+    if unknown:
+        raise ValueError(f"input sensors {unknown} are not built; built are {list(CAMERAS + NON_VISUAL_SENSORS)}")
+    cameras = tuple(c for c in CAMERAS if c in names)
+    if not cameras:
+        raise ValueError(f"input sensors {names} hold no camera; a model needs a non-empty subset of {list(CAMERAS)}")
+    return cameras, "an_object_is_in_hand" in names, "last_actions" in names
+
+
 class Tower(nn.Module):
-    """``DinoLLAMATxNavActorCritic`` (full-sensor configuration of dinov2_vits_tsfm_base.py:234-270)."""
+    """``DinoLLAMATxNavActorCritic`` (dinov2_vits_tsfm_base.py:234-270) over a sensor set: ``cameras`` (a non-empty subset of ``CAMERAS``), ``in_hand`` (the
+    an_object_is_in_hand embedding) and ``prev_actions`` (the previous-action embedding) -- what the reference's constructors take as uuids that may be None
+    (allenact_dino_transformer.py:67-68,129-132,517-527) and as ``input_sensors`` (early_fusion_tsfm_models.py:90-102).  Defaults: the full four-sensor set.
+    A sensor that is absent has no parameter in the arena (and no name in ``state_dict()``), no tokens in the fusion sequence and no term in the decoder input."""
 
     def __init__(self, arena: _Arena, device, n_fusion_layers=3, n_decoder_layers=3, max_steps=500, critic_type="linear",
-                 precision="bf16", dino_dim=DINO, text_encoder="t5-small", d_model=512, n_heads=8, n_heads_decoder=None):
+                 precision="bf16", dino_dim=DINO, text_encoder="t5-small", d_model=512, n_heads=8, n_heads_decoder=None,
+                 cameras=CAMERAS, in_hand=True, prev_actions=True):
         super().__init__()
+        self.cameras = tuple(c for c in CAMERAS if c in tuple(cameras))
+        if not self.cameras or len(self.cameras) != len(tuple(cameras)):
+            raise ValueError(f"cameras {list(cameras)}: a non-empty subset of {list(CAMERAS)} without repeats")
+        self.has_hand, self.has_prev = bool(in_hand), bool(prev_actions)
+        # fusion sequence of one row: [fusion token | ncam x 84 camera tokens | L text tokens] (text_cond_visual_encoder.py:203-219)
+        self.ncam = len(self.cameras)
+        self.text_off = 1 + self.ncam * NPATCH
         # transformer width of the fusion encoder AND the decoder (512 x 8 heads everywhere in the RL towers, allenact_dino_transformer.py:101-117; the imitation-
         # learning presets also use 768 x 12, early_fusion_tsfm_models.py:275-294); llama's SwiGLU hidden size follows from it (llama_model.py:330-334)
         n_heads_decoder = n_heads if n_heads_decoder is None else n_heads_decoder
@@ -191,8 +217,8 @@ class Tower(nn.Module):
         dec = arena.declare
         ve = self.visual_encoder = _NS()
         dec(ve, "fusion_token", (D,), "tok")
-        dec(ve, "visual_sensor_token_raw_navigation_camera", (D,), "tok")   # adjacent: [2, 512] camera-token table
-        dec(ve, "visual_sensor_token_raw_manipulation_camera", (D,), "tok")
+        for cam in self.cameras:                                            # adjacent: [ncam, D] camera-token table
+            dec(ve, f"visual_sensor_token_{cam}", (D,), "tok")
         ve.text_adapter = _seq(3)
         dec(ve.text_adapter[0], "weight", (D, self.text_dim), "lin"); dec(ve.text_adapter[0], "bias", (D,), "zeros")
         dec(ve.text_adapter[1], "weight", (D,), "ones"); dec(ve.text_adapter[1], "bias", (D,), "zeros")
@@ -220,8 +246,10 @@ class Tower(nn.Module):
         else:
             from .siglip_text import SIGLIP_TEXT_PRESETS, SigLIPTextFrozen
             ve.text_encoder = SigLIPTextFrozen(device, **SIGLIP_TEXT_PRESETS[text_encoder])
-        self.object_in_hand_embed = _NS(); dec(self.object_in_hand_embed, "weight", (3, D), "emb")
-        self.last_actions_embed = _NS(); dec(self.last_actions_embed, "weight", (N_ACTIONS + 2, D), "emb")
+        if self.has_hand:
+            self.object_in_hand_embed = _NS(); dec(self.object_in_hand_embed, "weight", (3, D), "emb")
+        if self.has_prev:
+            self.last_actions_embed = _NS(); dec(self.last_actions_embed, "weight", (N_ACTIONS + 2, D), "emb")
         self.time_encoder = _NS()
         self.time_encoder.register_buffer("div_term", torch.exp(torch.arange(0, D, 2) * (-math.log(10000.0) / D)).to(device))
         self.decoder = _NS()
@@ -288,9 +316,9 @@ class Tower(nn.Module):
             self._dw[key] = ar.flat_g[off:off + n * k].view(n, k)
             self._wt[key] = torch.empty(k, n, device=self.device_, dtype=self.adt)
         ve = self.visual_encoder
-        off, _ = ar.offsets[id(ve.visual_sensor_token_raw_navigation_camera)]
-        self._camtok = ar.flat_p[off:off + 2 * D].view(2, D)
-        self._dcamtok = ar.flat_g[off:off + 2 * D].view(2, D)
+        off, _ = ar.offsets[id(getattr(ve, f"visual_sensor_token_{self.cameras[0]}"))]
+        self._camtok = ar.flat_p[off:off + self.ncam * D].view(self.ncam, D)
+        self._dcamtok = ar.flat_g[off:off + self.ncam * D].view(self.ncam, D)
 
     def refresh_transposes(self):
         ar = self.arena
@@ -387,8 +415,11 @@ class Tower(nn.Module):
                 c["fusion"].append(saved)
         # decoder over the rollout time axis, rows (b*T + t); a pruned last fusion layer left the position-0 rows only
         xd = torch.empty(prep.R, D, device=self.device_, dtype=self.adt)
-        ops.decoder_embed_fwd(xf, D if nfl and self.prune_last else S * D, self.last_actions_embed.weight, self.object_in_hand_embed.weight,
-                              self.time_encoder.div_term, prep.prev_actions, prep.masks, prep.hand, prep.time_step, T, B, xd)
+        # an absent sensor's table and indices go in as None together (svla_decoder_embed_fwd: the term is skipped)
+        ops.decoder_embed_fwd(xf, D if nfl and self.prune_last else S * D, self.last_actions_embed.weight if self.has_prev else None,
+                              self.object_in_hand_embed.weight if self.has_hand else None, self.time_encoder.div_term,
+                              prep.prev_actions if self.has_prev else None, prep.masks if self.has_prev else None, prep.hand if self.has_hand else None,
+                              prep.time_step, T, B, xd)
         if T == 1 and not need_grad and prep.acting:
             # acting: one new token per env against the KV cache.  A one-step UPDATE batch (need_grad) takes the sequence form -- a sequence of length one has no
             # history to attend to, and the backward needs the saved activations -- and so does a batch whose Prep says ``acting = False`` (the imitation-learning
@@ -401,9 +432,11 @@ class Tower(nn.Module):
         return logits.view(T, B, N_ACTIONS), values.view(T, B, 1), (c if need_grad else None)
 
     def _inputs_fwd(self, prep, c, need_grad):
-        """Visual compressor + adapter (both cameras), frozen text encoder + text adapter, ``fusion_fill`` -> the fusion transformer's input rows [R * S, D]"""
+        """Visual compressor + adapter (all cameras), frozen text encoder + text adapter, ``fusion_fill`` -> the fusion transformer's input rows [R * S, D]"""
         D, R, S, L, U, ve, w = self.D, prep.R, prep.S, prep.L, prep.U, self.visual_encoder, self._w
-        M2 = R * 2 * NPATCH
+        if S != self.text_off + L or prep.tokens.numel() != R * self.ncam * NPATCH * self.dino_dim:
+            raise ValueError(f"inputs of {prep.tokens.numel() // max(R * NPATCH * self.dino_dim, 1)} camera(s), S = {S} for a tower of {self.ncam} camera(s), S = {self.text_off + L}")
+        M2 = R * self.ncam * NPATCH
         tok = prep.tokens.view(M2, self.dino_dim)
         # ReLU derivatives of the two compressor convs as 1 bit per element (like the feed-forward's): the input-gradient GEMMs then read
         # M2 x 64 mask bytes instead of re-reading a whole M2 x 512 bf16 activation
@@ -414,7 +447,7 @@ class Tower(nn.Module):
         a1 = ops.gemm_nt(c2, w["va"], M2, D, D, bias=ve.visual_adapter[0].bias)
         x = torch.empty(R, S, D, device=self.device_, dtype=self.adt)
         _, va_mean, va_rstd = ops.norm_fwd(a1, ve.visual_adapter[1].weight, ve.visual_adapter[1].bias, 1e-5, M2, relu=True,
-                                           tok=self._camtok, tok_group=NPATCH, y=x, ymap=(2 * NPATCH, S, 1), D=D)
+                                           tok=self._camtok, tok_group=NPATCH, y=x, ymap=(self.ncam * NPATCH, S, 1), D=D)
         t5_seed, key = (c["drop_seed"] if self.t5_dropout else None), prep.ids_key
         if t5_seed is None and key is not None and self._t5_cache[0] == key:
             t5 = self._t5_cache[1]     # eval mode: the frozen encoder is a pure function of the goal tokens (one episode = one goal)
@@ -424,7 +457,7 @@ class Tower(nn.Module):
             self._t5_cache = (key, t5) if (t5_seed is None and key is not None) else (None, None)
         ta = ops.gemm_nt(t5, w["ta"], U * L, D, self.text_dim, bias=ve.text_adapter[0].bias)
         tf, ta_mean, ta_rstd = ops.norm_fwd(ta, ve.text_adapter[1].weight, ve.text_adapter[1].bias, 1e-5, U * L, relu=True, D=D)
-        ops.fusion_fill(ve.fusion_token, tf, prep.gid, x, R, S, L, TEXT_OFF)
+        ops.fusion_fill(ve.fusion_token, tf, prep.gid, x, R, S, L, self.text_off)
         c.update(c1=c1, c2=c2, c1b=c1b, c2b=c2b, a1=a1, va=(va_mean, va_rstd), t5=t5, ta=ta, ta_stats=(ta_mean, ta_rstd))
         return x.view(R * S, D)
 
@@ -611,8 +644,9 @@ class Tower(nn.Module):
         # gradient of the fusion transformer's output: the position-0 rows only behind a pruned last layer, else all token rows (zero but for position 0)
         pruned = bool(c["fusion"]) and c["fusion"][-1]["pruned"]
         dyf = torch.empty(R, D, device=self.device_, dtype=self.adt) if pruned else ops.zeros(R, S, D, device=self.device_, dtype=self.adt).view(R * S, D)
-        ops.decoder_embed_bwd(dx, prep.prev_actions, prep.masks, prep.hand, T, B, dyf, D if pruned else S * D, g(self.last_actions_embed.weight),
-                              g(self.object_in_hand_embed.weight))
+        ops.decoder_embed_bwd(dx, prep.prev_actions if self.has_prev else None, prep.masks if self.has_prev else None, prep.hand if self.has_hand else None, T, B,
+                              dyf, D if pruned else S * D, g(self.last_actions_embed.weight) if self.has_prev else None,
+                              g(self.object_in_hand_embed.weight) if self.has_hand else None)
         site = self._site_fn(c.get("drop_seed"))
         drop_scale = 1.0 / (1.0 - self.dropout_p) if c.get("drop_seed") is not None else 1.0
         for i in reversed(range(len(c["fusion"]))):
@@ -736,7 +770,7 @@ class Tower(nn.Module):
         """backward of ``_inputs_fwd``: gradient of the fusion transformer's input rows -> fusion token, text adapter (frozen text encoder), visual adapter + compressor"""
         D, T, B, R, S, L, U = self.D, prep.T, prep.B, prep.R, prep.S, prep.L, prep.U
         ve, wt, dw, g, dev = self.visual_encoder, self._wt, self._dw, self.g, self.device_
-        M2 = R * 2 * NPATCH
+        M2 = R * self.ncam * NPATCH
         ops.colsum_acc(dx0, g(ve.fusion_token), R, D, row_stride=S)
         # text adapter (trainable) -- the T5 encoder is frozen (no_grad in the reference)
         dtf = ops.zeros(U * L, D, device=dev, dtype=F32)
@@ -744,21 +778,21 @@ class Tower(nn.Module):
             dtf_sh = torch.zeros(U * L * D, device=dev, dtype=torch.int64)
             ops.det_config(1, dtf, dtf_sh)
             try:
-                ops.fusion_text_bwd(dx0, prep.gid, T, B, S, L, TEXT_OFF, dtf)
+                ops.fusion_text_bwd(dx0, prep.gid, T, B, S, L, self.text_off, dtf)
                 ops.det_finalize(dtf, dtf_sh)
             finally:
                 ops.det_config(1, None, None)
         else:
-            ops.fusion_text_bwd(dx0, prep.gid, T, B, S, L, TEXT_OFF, dtf)
+            ops.fusion_text_bwd(dx0, prep.gid, T, B, S, L, self.text_off, dtf)
         dtf_b = torch.empty(U * L, D, device=dev, dtype=self.adt)
         ops.cast_bf16(dtf, dtf_b)
         dta = ops.norm_bwd(dtf_b, c["ta"], ve.text_adapter[1].weight, ve.text_adapter[1].bias, c["ta_stats"][0], c["ta_stats"][1], U * L,
                            g(ve.text_adapter[1].weight), g(ve.text_adapter[1].bias), relu=True, D=D)
         ops.gemm_tn_acc(dta, c["t5"], dw["ta"], U * L, D, self.text_dim, db=g(ve.text_adapter[0].bias))
-        # visual adapter + compressor (both cameras in one batch)
+        # visual adapter + compressor (all cameras in one batch)
         da1 = ops.norm_bwd(dx0, c["a1"], ve.visual_adapter[1].weight, ve.visual_adapter[1].bias, c["va"][0], c["va"][1], M2,
                            g(ve.visual_adapter[1].weight), g(ve.visual_adapter[1].bias), relu=True, dtok=self._dcamtok,
-                           tok_group=NPATCH, dymap=(2 * NPATCH, S, 1), D=D)
+                           tok_group=NPATCH, dymap=(self.ncam * NPATCH, S, 1), D=D)
         ops.gemm_tn_acc(da1, c["c2"], dw["va"], M2, D, D, db=g(ve.visual_adapter[0].bias))
         dc2 = self._relu_bwd_gemm(da1, wt["va"], M2, D, D, c["c2"], c["c2b"])
         ops.gemm_tn_acc(dc2, c["c1"], dw["c2"], M2, D, D, db=g(ve.visual_compressor[2].bias))
@@ -881,9 +915,9 @@ class T5Frozen(nn.Module):
 # ================================================================================================ shared per-call inputs
 class Prep:
     """Per-forward inputs shared by the three towers (built once).  Producers fill the fields one by one; a name that is not declared here is an AttributeError.
-    R = T * B rows of S fusion tokens; U unique goals of L tokens; tokens [R, 2, 84, dino_dim]; prev_actions, masks, hand, time_step [R]; traj_bt [B, T]; ids,
-    attn_mask [U, L]; gid [R]: row -> goal.  Optional: ``acting`` (a T = 1 pass under no_grad is a step against the KV caches), ``ids_key`` (host-side identity of
-    the goals: eval-mode text-feature cache), ``attn_mask_u8`` (attn_mask in the kernels' format), ``kvalid_static`` (recorded steps: the KV-window mask [B, max_steps])."""
+    R = T * B rows of S = 1 + ncam * 84 + L fusion tokens; U unique goals of L tokens; tokens [R, ncam, 84, dino_dim]; prev_actions, masks, hand, time_step [R]
+    (hand: None without the in-hand sensor; prev_actions, masks: None without the previous-action sensor); traj_bt [B, T]; ids, attn_mask [U, L]; gid [R]: row -> goal.
+    Optional: ``acting`` (a T = 1 pass under no_grad is a step against the KV caches), ``ids_key`` (host-side identity of the goals: eval-mode text-feature cache), ``attn_mask_u8`` (attn_mask in the kernels' format), ``kvalid_static`` (recorded steps: the KV-window mask [B, max_steps])."""
     __slots__ = ("T", "B", "R", "S", "L", "U", "tokens", "prev_actions", "masks", "hand", "time_step", "traj_bt", "ids", "attn_mask", "gid",
                  "acting", "ids_key", "attn_mask_u8", "kvalid_static")
 
@@ -928,18 +962,25 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
     def __init__(self, device="cuda", tokenizer: Optional[GoalTokenizer] = None, max_steps: int = 500,
                  goal_sensor_uuid="natural_language_spec", rgb_dino_preprocessor_uuid="rgb_dinov2",
                  manipulation_rgb_dino_preprocessor_uuid="manipulation_rgb_dinov2", an_object_is_in_hand_uuid="an_object_is_in_hand",
-                 time_step_uuid="time_step", traj_idx_uuid="traj_index", critic_type: str = "linear", precision: str = "bf16", **unused):
+                 time_step_uuid="time_step", traj_idx_uuid="traj_index", critic_type: str = "linear", precision: str = "bf16", full_sensor: bool = True, **unused):
+        """``manipulation_rgb_dino_preprocessor_uuid=None`` / ``an_object_is_in_hand_uuid=None``: towers without the manipulation camera / the in-hand sensor, as the
+        reference's constructor takes them (allenact_dino_transformer.py:67-68); ``full_sensor=False`` sets both to None, the navigation-only configuration of
+        ``DinoV2ViTSTSFMBaseParams.full_sensor`` (dinov2_vits_tsfm_base.py:86,227-232).  The RL towers always embed the previous action (``add_prev_actions=True``)."""
+        if not full_sensor:
+            manipulation_rgb_dino_preprocessor_uuid = an_object_is_in_hand_uuid = None
         if not torch.cuda.is_available():
             raise RuntimeError("safevla_amd needs an MI355X: there is no CPU or eager fallback for the policy kernels")
         ops.lib()  # fail loudly if the HIP extension is missing
         arena = _Arena()
         device = torch.device(device)
         arena.begin_tower()
-        super().__init__(arena, device, max_steps=max_steps, critic_type=critic_type, precision=precision)      # every tower is built from the same kwargs
+        kw = dict(max_steps=max_steps, critic_type=critic_type, precision=precision, in_hand=an_object_is_in_hand_uuid is not None,      # every tower is built from the same kwargs
+                  cameras=CAMERAS[:1] if manipulation_rgb_dino_preprocessor_uuid is None else CAMERAS)
+        super().__init__(arena, device, **kw)
         arena.begin_tower()
-        self.critic_tsfm = Tower(arena, device, max_steps=max_steps, critic_type=critic_type, precision=precision)
+        self.critic_tsfm = Tower(arena, device, **kw)
         arena.begin_tower()
-        self.c_critic_tsfm = Tower(arena, device, max_steps=max_steps, critic_type=critic_type, precision=precision)
+        self.c_critic_tsfm = Tower(arena, device, **kw)
         arena.build(device)
         self.towers = [self, self.critic_tsfm, self.c_critic_tsfm]
         for t in self.towers:
@@ -964,6 +1005,20 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
             self.enable_acting_plans(True)              # recorded single-step launches are the default acting path
         self._goal_cache: Dict[int, List[int]] = {}
         self.sync_weights()
+
+    @property
+    def full_sensor(self) -> bool:
+        return self.ncam == 2 and self.has_hand
+
+    def mask_non_nav_actions(self):
+        """Navigation-only policy: the actor tower's bias of every action outside the reference's navigation set becomes -999999 (dinov2_vits_tsfm_base.py:287-289,
+        after the IL checkpoint is loaded), so those actions have probability exactly 0 -- exp(-1e6 - max) underflows to 0 in fp32 -- and are never sampled."""
+        from .agent import ALL_STRETCH_ACTIONS, NAV_ACTIONS
+        idx = [i for i, a in enumerate(ALL_STRETCH_ACTIONS) if a not in NAV_ACTIONS]
+        with torch.no_grad():
+            self.actor.linear.bias[torch.as_tensor(idx, device=self.device_)] = -999999.0
+        self.sync_weights(frozen=False)
+        return idx
 
     # ---- AllenAct ActorCriticModel API bits -------------------------------------------------------------------
     @property
@@ -1040,15 +1095,15 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         dev = self.device_
         p = Prep()
         p.T, p.B, p.R = T, B, R
-        if "dino_tokens" in observations:       # storage-native layout [T,B,2,84,384] bf16
-            p.tokens = observations["dino_tokens"].reshape(R, 2, NPATCH, self.dino_dim).to(self.adt).contiguous()
+        if "dino_tokens" in observations:       # storage-native layout [T,B,ncam,84,384] bf16
+            p.tokens = observations["dino_tokens"].reshape(R, self.ncam, NPATCH, self.dino_dim).to(self.adt).contiguous()
         else:
-            p.tokens = torch.empty(R, 2, NPATCH, self.dino_dim, device=dev, dtype=self.adt)
-            ops.feat_to_tokens(observations[u["nav"]].reshape(R, self.dino_dim, NPATCH).contiguous(), p.tokens, 0)
-            ops.feat_to_tokens(observations[u["manip"]].reshape(R, self.dino_dim, NPATCH).contiguous(), p.tokens, 1)
+            p.tokens = torch.empty(R, self.ncam, NPATCH, self.dino_dim, device=dev, dtype=self.adt)
+            for cam, key in enumerate((u["nav"], u["manip"])[:self.ncam]):
+                ops.feat_to_tokens(observations[key].reshape(R, self.dino_dim, NPATCH).contiguous(), p.tokens, cam, ncam=self.ncam)
         p.prev_actions = prev_actions.reshape(R).contiguous()
         p.masks = masks.reshape(R).to(F32).contiguous()
-        p.hand = observations[u["hand"]].reshape(R).contiguous()
+        p.hand = observations[u["hand"]].reshape(R).contiguous() if self.has_hand else None
         p.time_step = observations[u["time"]].reshape(R).contiguous()
         p.traj_bt = observations[u["traj"]].reshape(T, B).t().contiguous().to(torch.int32)
         # goals: content-hash rows on the GPU, tokenise each unique string once on the host
@@ -1094,7 +1149,7 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         p.gid = inv.to(torch.int32).contiguous()
         p.attn_mask_u8 = p.attn_mask.to(torch.uint8).contiguous()      # T5 key-padding mask in the kernels' format (once, not per tower)
         p.U, p.L = p.ids.shape
-        p.S = TEXT_OFF + p.L
+        p.S = self.text_off + p.L
         return p
 
     # ---- small shapes: the three (independent) towers on three HIP streams ------------------------------------------------------
@@ -1152,9 +1207,10 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         dev = self.device_
         if st is None:
             st = _ActingState()
-            st.T, st.B, st.R, st.U, st.L, st.S = 1, B, B, B, L, TEXT_OFF + L
+            st.T, st.B, st.R, st.U, st.L, st.S = 1, B, B, B, L, self.text_off + L
             z = lambda *shape, dtype=torch.int64: torch.zeros(*shape, device=dev, dtype=dtype)
-            st.tokens, st.prev_actions, st.masks, st.hand, st.time_step = z(B, 2, NPATCH, self.dino_dim, dtype=self.adt), z(B), z(B, dtype=F32), z(B), z(B)
+            st.tokens, st.prev_actions, st.masks, st.time_step = z(B, self.ncam, NPATCH, self.dino_dim, dtype=self.adt), z(B), z(B, dtype=F32), z(B)
+            st.hand = z(B) if self.has_hand else None
             st.traj_bt, st.ids, st.attn_mask = z(B, 1, dtype=torch.int32), z(B, L), torch.ones(B, L, device=dev, dtype=torch.int64)
             st.gid, st.t_dev, st.attn_mask_u8 = torch.arange(B, device=dev, dtype=torch.int32), z(()), torch.ones(B, L, device=dev, dtype=torch.uint8)
             st.kvalid_static = z(B, self.max_steps, dtype=torch.uint8) if plan_mode else None
@@ -1167,7 +1223,9 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         for t in self.towers:
             t.refresh_folded()          # (recorded / captured steps do not run the Python that would notice an optimiser step: refresh the gamma-folded weights here, in place)
         # per-step inputs -> static buffers
-        st.tokens.copy_(prep.tokens); st.prev_actions.copy_(prep.prev_actions); st.masks.copy_(prep.masks); st.hand.copy_(prep.hand)
+        st.tokens.copy_(prep.tokens); st.prev_actions.copy_(prep.prev_actions); st.masks.copy_(prep.masks)
+        if self.has_hand:
+            st.hand.copy_(prep.hand)
         st.time_step.copy_(prep.time_step)
         st.ids.copy_(prep.ids[prep.gid.long()]); st.attn_mask.copy_(prep.attn_mask[prep.gid.long()])
         st.attn_mask_u8.copy_(st.attn_mask)
@@ -1249,10 +1307,10 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         if st is None or st.plans is None or not st.grouped_ok:
             return None
         u = self.uuids
-        hand, ts = observations.get(u["hand"]), observations.get(u["time"])
+        hand, ts = (observations.get(u["hand"]) if self.has_hand else None), observations.get(u["time"])      # no in-hand sensor: nothing is read, the stage gets a NULL pair
         i64 = torch.int64
-        if hand is None or ts is None or not (tk.dtype == self.adt and tk.is_contiguous() and tk.numel() == st.tokens.numel() and prev_actions.dtype == i64 and prev_actions.is_contiguous()
-                                              and masks.dtype == F32 and masks.is_contiguous() and masks.numel() == B and hand.dtype == i64 and hand.is_contiguous() and hand.numel() == B
+        if (self.has_hand and hand is None) or ts is None or not (tk.dtype == self.adt and tk.is_contiguous() and tk.numel() == st.tokens.numel() and prev_actions.dtype == i64 and prev_actions.is_contiguous()
+                                              and masks.dtype == F32 and masks.is_contiguous() and masks.numel() == B and (hand is None or (hand.dtype == i64 and hand.is_contiguous() and hand.numel() == B))
                                               and ts.dtype == i64 and ts.is_contiguous() and ts.numel() == B and ids.dtype == i64 and ids.is_contiguous() and ids.numel() == B * L):
             return None
         for t in self.towers:

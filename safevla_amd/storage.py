@@ -9,8 +9,8 @@ the reference: ``initialize(observations, num_samplers, recurrent_memory_specifi
 ``batched_experience_generator`` (keys consumed by SafePPOLogGrad: training/online/loss/customized_loss.py:327-385).
 
 HBM layout (MI355X-first): everything lives in preallocated [T+1, B, ...] / [T, B] device tensors; DINO features can
-be held as bf16 tokens [T+1, B, 2, 84, 384] (``dino_tokens``, 2.7x smaller than fp32 channels-first and already in
-the layout the compressor GEMM wants); GAE for rewards and costs is one fused kernel launch.
+be held as bf16 tokens [T+1, B, ncam, 84, 384] (``dino_tokens``, 2.7x smaller than fp32 channels-first and already in
+the layout the compressor GEMM wants; ncam = 1 with ``manip_uuid=None``, the navigation-only towers); GAE for rewards and costs is one fused kernel launch.
 """
 from typing import Dict, Iterator, Optional
 
@@ -26,6 +26,7 @@ class RolloutStorage:
         self.device = torch.device(device)
         self.store_tokens = store_tokens
         self.nav_uuid, self.manip_uuid = nav_uuid, manip_uuid
+        self.cam_uuids = (nav_uuid,) if manip_uuid is None else (nav_uuid, manip_uuid)      # camera slot of ``dino_tokens`` = position here
         self.step = 0
         self.B = 0
         self.observations: Dict[str, torch.Tensor] = {}
@@ -41,11 +42,11 @@ class RolloutStorage:
         self.B = B
         self.observations = {}
         for k, v in obs.items():
-            if self.store_tokens and k in (self.nav_uuid, self.manip_uuid):
+            if self.store_tokens and k in self.cam_uuids:
                 continue
             self.observations[k] = torch.zeros((T + 1, B) + tuple(v.shape[1:]), device=dev, dtype=v.dtype)
         if self.store_tokens and self.nav_uuid in obs:
-            self.observations["dino_tokens"] = torch.zeros(T + 1, B, 2, 84, 384, device=dev, dtype=torch.bfloat16)
+            self.observations["dino_tokens"] = torch.zeros(T + 1, B, len(self.cam_uuids), 84, 384, device=dev, dtype=torch.bfloat16)
         f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
         self.masks = f(T + 1, B, 1)
         self.value_preds, self.c_value_preds = f(T + 1, B, 1), f(T + 1, B, 1)
@@ -62,9 +63,8 @@ class RolloutStorage:
 
     def _insert_obs(self, obs, t):
         for k, v in obs.items():
-            if self.store_tokens and k in (self.nav_uuid, self.manip_uuid):
-                cam = 0 if k == self.nav_uuid else 1
-                ops.feat_to_tokens(v.reshape(self.B, 384, 84).contiguous().float(), self.observations["dino_tokens"][t], cam)
+            if self.store_tokens and k in self.cam_uuids:
+                ops.feat_to_tokens(v.reshape(self.B, 384, 84).contiguous().float(), self.observations["dino_tokens"][t], self.cam_uuids.index(k), ncam=len(self.cam_uuids))
             else:
                 self.observations[k][t].copy_(v.reshape(self.observations[k][t].shape))
 

@@ -46,8 +46,10 @@ class SynthSpec:
 
 
 def fill_synthetic_rollout(model, spec: SynthSpec, device="cuda") -> Tuple[RolloutStorage, Dict[str, torch.Tensor], Dict[str, float]]:
-    """Returns (storage filled with T steps, {next_value, next_c_value}, {episode_cost_sum, n_episodes})."""
+    """Returns (storage filled with T steps, {next_value, next_c_value}, {episode_cost_sum, n_episodes}).  Only the observations of the model's sensor set are
+    emitted: ``ncam`` cameras in ``dino_tokens``, ``an_object_is_in_hand`` only for a model with that sensor."""
     T, B, L = spec.T, spec.B, spec.L
+    ncam, has_hand = getattr(model, "ncam", 2), getattr(model, "has_hand", True)
     rs = np.random.RandomState(spec.seed)
     tasks = env_tasks(spec.task, B, spec.env_offset)
     done_p = np.array([TASK_DONE_P.get(t, 1.0 / 60) for t in tasks])
@@ -81,16 +83,18 @@ def fill_synthetic_rollout(model, spec: SynthSpec, device="cuda") -> Tuple[Rollo
         cur_t = cur_t + 1
     dev = torch.device(device)
     g = torch.Generator(device=dev).manual_seed(spec.seed)
-    st = RolloutStorage(T, device=dev, store_tokens=True)
+    st = RolloutStorage(T, device=dev, store_tokens=True, **({} if ncam == 2 else dict(manip_uuid=None)))
     st.T, st.B = T, B
     f = lambda *s: torch.zeros(*s, device=dev, dtype=torch.float32)
     st.observations = {
-        "dino_tokens": torch.randn(T + 1, B, 2, 84, 384, device=dev, dtype=torch.float32, generator=g).to(torch.bfloat16),
+        "dino_tokens": torch.randn(T + 1, B, ncam, 84, 384, device=dev, dtype=torch.float32, generator=g).to(torch.bfloat16),
         "goal_token_ids": torch.from_numpy(goal).to(dev),
         "time_step": torch.from_numpy(time_step).to(dev),
         "traj_index": torch.from_numpy(traj).to(dev),
         "an_object_is_in_hand": torch.from_numpy((rs.rand(T + 1, B, 1) < hand_p[None, :, None]).astype(np.int64)).to(dev),
     }
+    if not has_hand:
+        del st.observations["an_object_is_in_hand"]
     st.masks = torch.from_numpy(masks).to(dev)
     st.rewards, st.costs = torch.from_numpy(rewards).to(dev), torch.from_numpy(costs).to(dev)
     st.prev_actions = torch.from_numpy(rs.randint(0, 20, size=(T + 1, B)).astype(np.int64)).to(dev)
@@ -123,8 +127,9 @@ class SynthVectorEnv:
     END_ACTION = 4          # ALL_STRETCH_ACTIONS[4] == "end" (utils/constants/stretch_initialization_utils.py:145-166)
 
     def __init__(self, B: int, L: int = 12, task: str = "ObjectNav", seed: int = 0, max_steps: int = 500, cost_p: float = 0.05,
-                 device="cuda", env_offset: int = 0, store_tokens: bool = True):
+                 device="cuda", env_offset: int = 0, store_tokens: bool = True, full_sensor: bool = True):
         self.B, self.L, self.max_steps, self.cost_p = B, L, max_steps, cost_p
+        self.full_sensor = full_sensor      # False: the navigation-only sensor set -- no manipulation camera, no ``an_object_is_in_hand``
         self.dev = torch.device(device)
         self.g = torch.Generator(device=self.dev).manual_seed(seed)
         self.tasks = env_tasks(task, B, env_offset)
@@ -148,13 +153,15 @@ class SynthVectorEnv:
 
     def observations(self) -> Dict[str, torch.Tensor]:
         B = self.B
-        obs = {"goal_token_ids": self.goal.clone(), "time_step": self.time_step.clone(), "traj_index": self.traj.clone(),
-               "an_object_is_in_hand": (self._rand(B, 1) < self.hand_p[:, None]).to(torch.int64)}
+        obs = {"goal_token_ids": self.goal.clone(), "time_step": self.time_step.clone(), "traj_index": self.traj.clone()}
+        if self.full_sensor:
+            obs["an_object_is_in_hand"] = (self._rand(B, 1) < self.hand_p[:, None]).to(torch.int64)
         if self.store_tokens:
-            obs["dino_tokens"] = torch.randn(B, 2, 84, 384, device=self.dev, generator=self.g).to(torch.bfloat16)
+            obs["dino_tokens"] = torch.randn(B, 2 if self.full_sensor else 1, 84, 384, device=self.dev, generator=self.g).to(torch.bfloat16)
         else:
             obs["rgb_dinov2"] = torch.randn(B, 384, 7, 12, device=self.dev, generator=self.g)
-            obs["manipulation_rgb_dinov2"] = torch.randn(B, 384, 7, 12, device=self.dev, generator=self.g)
+            if self.full_sensor:
+                obs["manipulation_rgb_dinov2"] = torch.randn(B, 384, 7, 12, device=self.dev, generator=self.g)
         return obs
 
     def reset(self) -> Dict[str, torch.Tensor]:

@@ -29,6 +29,9 @@ def build_parser():
     ap.add_argument("--lr", type=float, default=2e-5)
     ap.add_argument("--save_interval", type=int, default=50_000)
     ap.add_argument("--il_ckpt_path", default=None)
+    ap.add_argument("--full_sensor", type=lambda v: {"true": True, "false": False}[str(v).lower()], default=True, metavar="{true,false}",
+                    help="false: navigation-only towers (no manipulation camera, no in-hand sensor) and the non-navigation actions masked out "
+                         "(DinoV2ViTSTSFMBaseParams.full_sensor, dinov2_vits_tsfm_base.py:86,227-232,287-289)")
     ap.add_argument("--wandb_project", default="")
     ap.add_argument("--wandb_entity", default="")
     # OnPolicyRunnerMixin
@@ -92,10 +95,12 @@ def main(argv=None):
     # replica must hold the same function; per-rank streams (sampling, synthetic environments) start afterwards
     torch.manual_seed(args.seed or 0)
     env0, B = parallel.shard_envs(args.num_train_processes, world, rank)
-    model = SafeDinoLLAMATxNavActorCriticSeparate(device=dev, max_steps=args.max_steps)
+    model = SafeDinoLLAMATxNavActorCriticSeparate(device=dev, max_steps=args.max_steps, full_sensor=args.full_sensor)
     torch.manual_seed((args.seed or 0) + 1 + rank)
     if args.il_ckpt_path:
         init_towers_from_il(model, args.il_ckpt_path)
+    if not args.full_sensor:
+        model.mask_non_nav_actions()          # after the IL checkpoint, as the reference does
     cfg = PPOLagConfig(lr=args.lr, cost_limit=args.cost_limit if args.cost_limit is not None else 1e9)
     eng = PPOLagEngine(model, cfg)
     step = 0
@@ -110,8 +115,8 @@ def main(argv=None):
     T = args.num_steps
     env = st = None
     if args.collect == "acting":
-        env = SynthVectorEnv(B, L=args.goal_tokens, task=args.task, seed=1234 + rank, max_steps=args.max_steps, device=dev, env_offset=env0)
-        st = RolloutStorage(T, device=dev, store_tokens=True)
+        env = SynthVectorEnv(B, L=args.goal_tokens, task=args.task, seed=1234 + rank, max_steps=args.max_steps, device=dev, env_offset=env0, full_sensor=args.full_sensor)
+        st = RolloutStorage(T, device=dev, store_tokens=True, **({} if args.full_sensor else dict(manip_uuid=None)))
         st.initialize(env.reset(), num_samplers=B)
     while step < budget:
         t0 = time.time()
