@@ -96,18 +96,21 @@ int svla_gemm_nt_bf16(const svla_bf16* A, long lda, const svla_bf16* B, long ldb
                       long ldr, const svla_bf16* relu_mask, long ldm, void* C, long ldc, int M, int N, int K, int act,
                       int out_f32, float alpha, unsigned char* relu_bits_out, const unsigned char* relu_bits,
                       const svla_dropout* drop, void* stream);
-/* Kernel choice behind svla_gemm_nt_bf16 (all the same arithmetic; bf16 output, fp32 accumulation, one rounding): generated gfx950 assembly for the row-streaming
- * shapes of the update -- K = 512 without a residual: A-stationary kernels (asmgen/nt_as_gen.py: bias / ReLU + sign bits [+ dropout] / sign-bit mask), and their
- * K = 384 flavours (bias / ReLU + sign bits / erf-GELU: the frozen ViT-S/14's qkv and fc1, the policy's visual compressor); K >= 384 (K % 128 == 0, N % 256 == 0)
- * without dropout: output-stationary kernels (asmgen/nt_os_gen.py: bias and / or residual), from ~4 tiles per CU up.  The A-stationary kernels have two launch
- * shapes: from two 256-row panels per CU up one persistent workgroup per CU sweeps all of N per panel; below that ("mid-M": the 233 panels of the batch-256 probe,
- * the ViT's 216) the grid is (panel slots) x (n-ranges) and a cost model calibrated on profiles/r05_midm_sweep.txt decides between it and the tile kernels (an
- * acting step's 45 panels stay on the tile kernels).  M % 256 tail rows run on the 128-tile kernel -- else the 8-phase 256-tile HIP kernel (>= 160 tiles), else
- * the 128-tile HIP kernel.  ACT_GELU is the erf-GELU of nn.GELU() evaluated as x (1/2 + clamp(t P(z))) with a degree-9 polynomial (asmgen/gelu_poly.py:
- * |error| <= 2.2e-5 for all x, exact tails) in every kernel.
- * Test / A-B hook: on = 1 forces the 128x128-tile kernel, 2 the 256-tile / assembly kernels wherever their shape constraints hold (incl. the mid-M launch whatever the
- * cost model says), 0 = normal dispatch; on = 10 + flags: 8192 = every assembly kernel off, 16384 = the output-stationary ones off (tools/ab_*.py), smaller flags =
- * timing-only ablations of the HIP kernels.  Any value also performs the one-time device-side initialisation of the dispatchers (the binding calls it with 0 at load). */
+/* Kernel choice behind svla_gemm_nt_bf16 / svla_gemm_tn_f32acc (all the same arithmetic; bf16 output, fp32 accumulation, one rounding).  The rules -- eligibility,
+ * thresholds, the mid-M cost model, grids -- are stated once, in safevla_amd/csrc/gemm_host.h (nt_plan / tn_plan: a pure function of the problem, the knobs below and
+ * the CU count, with no HIP in it); the entry points launch what it returns, and svla_gemm_nt_plan / svla_gemm_tn_plan below return the same answer without a GPU.
+ * In outline, NT, first match: the A-stationary assembly kernels (asmgen/nt_as_gen.py; K = 512 or 384, no residual: one row per flavour in NT_AS_FLAVOURS; from two
+ * 256-row panels per CU up one persistent workgroup per CU, below that a (panel slots) x (n-ranges) grid when the cost model has it ahead of the tile kernels); the
+ * output-stationary assembly kernels (asmgen/nt_os_gen.py; K >= 384, bias and / or residual, no dropout, from ~4 tiles per CU up); the 8-phase 256-tile HIP kernel
+ * (from SVLA_NT256_MIN_TILES = 160 tiles up); the 128-tile HIP kernel, which also runs the M % 256 rows behind an assembly launch.  TN: svla_tn_os (asmgen/
+ * tn_os_gen.py) or, in deterministic mode, the 8-phase 256-tile kernel for N, K % 256 == 0 and M % 64 == 0 from 16 k rows up (8 k when N K >= 512 k); else the
+ * 128-tile kernel behind a column sum for the bias gradient.  ACT_GELU is the erf-GELU of nn.GELU() evaluated as x (1/2 + clamp(t P(z))) with a degree-9 polynomial
+ * (asmgen/gelu_poly.py: |error| <= 2.2e-5 for all x, exact tails) in every kernel.
+ * Test / A-B hook (GemmKnobs): on = 1 forces the 128x128-tile kernels, 2 the 256-tile / assembly kernels wherever their shape constraints hold (incl. the mid-M launch
+ * whatever the cost model says; TN: whole 64-row groups, the ragged rest on the 128-tile kernel), 0 = normal dispatch; on = 10 + flags (GEMM_DBG_*): 8192 = every
+ * assembly kernel off, 16384 = the output-stationary NT ones off, 128 = the 2-buffer 256-tile kernels (tools/ab_*.py), smaller flags = timing-only ablations of the
+ * HIP kernels.  Any value also performs the one-time device-side initialisation of the dispatchers (the binding calls it with 0 at load); without a device that
+ * fails (-1) and the hook is set all the same. */
 int svla_gemm_force_small_tile(int on);
 /* RMSNorm(A) . W'^T for small M: C[m, n] = epi(rstd[m] * sum_k A[m, k] W'[n, k]), rstd[m] = rsqrt(mean_k A[m, k]^2 + eps), W' = W diag(gamma) folded by the
  * caller -- the pre-norm linears of the frozen T5 encoder block (T5LayerNorm -> q | k | v, -> wi: allenact_dino_transformer.py:506-508 runs HF's T5EncoderModel) and of
@@ -120,6 +123,15 @@ int svla_gemm_nt_rmsa_bf16(const svla_bf16* A, long lda, const svla_bf16* B, lon
  * svla_gemm_nt_bf16 / svla_gemm_tn_f32acc call of this process launched for its main problem ("svla_nt_as_f0", "svla_nt_os_br", "svla_tn_os",
  * "gemm_nt8p_bf16_kernel", "gemm_nt_bf16_kernel", ...): the kernel-choice tests assert the generated assembly really ran (same cited layers). */
 int svla_gemm_last_kernel(char* name, int cap, int* mnk);
+/* Read-only: what svla_gemm_nt_bf16 / svla_gemm_tn_f32acc would launch for a problem on a device of n_cu compute units, under the hook's current state, with every
+ * assembly kernel counted as present (same cited layers).  No HIP call: they run without a GPU.  kernel: the name svla_gemm_last_kernel would show (cap bytes).
+ * epilogue: 1 bias | 2 residual | 4 relu_mask | 8 relu_bits | 16 relu_bits_out.  -1: a shape or activation the GEMM entry refuses (its other checks are not repeated: the plan of such a call means nothing).
+ * svla_gemm_nt_plan  out[10] = path (0 A-stationary asm, 1 output-stationary asm, 2 8-phase, 3 2-buffer, 4 128-tile), rows of the main launch, tail rows (128-tile
+ *   kernel behind it), grid_x, grid_y, A-stationary nr / flags / cmask (else 0), the log's extra bytes per row, 1 if the log line is written without SVLA_GEMM_LOG_ALL.
+ * svla_gemm_tn_plan  out[12] = main part, tail part (rows 0: none; the ragged rows of a forced call), each: path (0 svla_tn_os, 1 8-phase, 2 2-buffer, 3 128-tile),
+ *   rows, chunk_rows, grid, 1 if svla_colsum_bf16 runs in front, 1 if svla_gemm_last_kernel records the launch; kernel = "main" or "main+tail". */
+int svla_gemm_nt_plan(int M, int N, int K, int act, int out_f32, int epilogue, float alpha, int drop_on, int row_mult, int n_cu, char* kernel, int cap, int* out);
+int svla_gemm_tn_plan(int M, int N, int K, int has_db, int det_on, int n_cu, char* kernel, int cap, int* out);
 /* Tool / test hook: launch kernel `name` of the embedded gfx950 assembly code object (safevla_amd/asmgen/) with a raw kernarg block --
  * probes of the assembly builder's instruction semantics on hardware (tools/asm_probe.py); the GEMM entry points above dispatch to the
  * generated kernels themselves (same cited layers). */

@@ -909,7 +909,7 @@ class NtAsGen(KernelGen):
         return self
 
 
-# flavour -> generator options (the C dispatcher nt_as_try of csrc/gemm.hip picks by name)
+# flavour -> generator options (NT_AS_FLAVOURS of csrc/gemm_host.h picks by name)
 FLAVOURS = {
     "f0": dict(),                                               # bias (or none): in_proj forward, out_proj input gradient
     "f1d": dict(relu=True, bits_out=True, drop=True),           # bias, ReLU, dropout, sign bits out: linear1 forward in train mode

@@ -560,7 +560,7 @@ class NtOsGen(KernelGen):
         return self
 
 
-# flavour -> generator options (the C dispatcher nt_os_try of csrc/gemm.hip picks by name)
+# flavour -> generator options (nt_os_plan of csrc/gemm_host.h picks by name)
 FLAVOURS = {"p": dict(), "b": dict(bias=True), "r": dict(res=True), "br": dict(bias=True, res=True)}
 
 if _os.environ.get("SVLA_ASM_DEBUG_VARIANTS"):      # timing-only builds (tools/var_nt_os.py): wrong results

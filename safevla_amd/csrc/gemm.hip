@@ -17,6 +17,7 @@
 // tile order so the tiles that share an operand panel run on one XCD's L2.
 #include "common.h"
 #include "asm_kernels.h"
+#include "gemm_host.h"      // ACT_*, GEMM_DBG_*, GemmKnobs, nt_plan / tn_plan: which kernel carries a call
 #include <cstdlib>
 #include <cstring>
 #include <cstdio>
@@ -38,8 +39,6 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
 }
 
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2 };
-
 struct GemmNtArgs {
     const bf16_t* A; long lda;
     const bf16_t* B; long ldb;
@@ -53,8 +52,7 @@ struct GemmNtArgs {
     const unsigned char* bits_in;     // ReLU mask given as such bits instead of a bf16 activation tensor (relu_mask)
     DropCfg drop;                     // train-mode dropout after the activation, before the residual add (thr == 0: off)
     int row0;         // global row index of A's row 0 (dropout counter / sign-bit block of the M-tail sub-problem behind the assembly kernels); 128-tile kernel only
-    int dbg;          // timing-only ablations of the 256-tile kernel (tools/ab_gemm.py, tools/shape_gemm.py): 1 = no C stores,
-                      // 2 = no epilogue, 64 = no fragment reads / MFMAs (operand DMA stream + barriers alone)
+    int dbg;          // timing-only ablations of the 256-tile kernel (tools/ab_gemm.py, tools/shape_gemm.py): GEMM_DBG_* of gemm_host.h
     float rms_eps;    // > 0 (svla_gemm_nt_rmsa_bf16, 128-tile kernel only): row m of the product is scaled by rsqrt(mean_k A[m,k]^2 + rms_eps) -- RMSNorm(A) . W^T
                       // with the norm's gamma folded into W; the row sums of squares fall out of the A fragments the MFMAs read anyway
 };
@@ -404,7 +402,7 @@ struct Nt256Epi {
     __device__ __forceinline__ bool run(f32x16 (&acc)[4][2], int m0, int n0) {
         char* C = (char*)p.C;
         const bool wave_cols_valid = n0 + wn * 64 < p.N;      // wave-uniform: a wave's 64 output columns are all inside N or all outside
-        if ((p.dbg & 2) || !wave_cols_valid) {
+        if ((p.dbg & GEMM_DBG_NO_EPILOGUE) || !wave_cols_valid) {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -507,7 +505,7 @@ struct Nt256Epi {
             for (int it = 0; it < 4; ++it) {
                 const int r0 = mrow0 + it * 8;
                 char* cb = C + ((size_t)r0 * p.ldc + n0 + wn * 64) * 2;
-                if (p.dbg & 1) { asm volatile("" ::"v"(w[it])); }
+                if (p.dbg & GEMM_DBG_NO_STORES) { asm volatile("" ::"v"(w[it])); }
                 else if (r0 + 8 <= p.M) *(u32x4*)(cb + c_loff) = w[it];
                 else if (r0 + (lo >> 3) < p.M) *(u32x4*)(cb + c_loff) = w[it];
             }
@@ -562,7 +560,7 @@ struct Nt256Epi {
                 __builtin_amdgcn_wave_barrier();
             }
         }
-        return (m0 + 256 <= p.M) && !(p.dbg & 3);
+        return (m0 + 256 <= p.M) && !(p.dbg & (GEMM_DBG_NO_STORES | GEMM_DBG_NO_EPILOGUE));
     }
 };
 
@@ -678,7 +676,7 @@ __device__ __forceinline__ void gemm_nt256k64_bf16_kernel_body(GemmNtArgs p) {
                     B2[t] = *(const bf16x8*)(Bb + r_ * BK64 + swz64(r_, kk * 2 + fh) * 8);
                 }
             };
-            if (p.dbg & 64) continue;          // timing-only: DMA stream + barriers alone (what does the operand fetch path sustain?)
+            if (p.dbg & GEMM_DBG_DMA_ONLY) continue;          // timing-only: DMA stream + barriers alone (what does the operand fetch path sustain?)
             load_frags(0, fa[0], fb[0]);
 #pragma unroll
             for (int kk = 0; kk < BK64 / 16; ++kk) {
@@ -774,9 +772,9 @@ __device__ __forceinline__ void gemm_nt8p_bf16_kernel_body(GemmNtArgs p) {
     set_dma_tile();
     // ty: 0 = B0, 1 = B1, 2 = A0, 3 = A1 (compile-time at every call site); ring slot = 4 * (K-tile parity) + ty
     auto issue = [&](const int ty) {
-        if (d_live && !(p.dbg & 32)) {      // timing-only: dbg & 32 = no DMA at all, dbg & 8 = always K-tile 0 of the first tile (L2-resident operands)
-            const char* base = (p.dbg & 8) ? (ty >= 2 ? (const char*)p.A : (const char*)p.B) : (ty >= 2 ? a_base : b_base);
-            const uint32_t kb = (p.dbg & 8) ? 0u : (uint32_t)(d_kt * BK64 * 2);
+        if (d_live && !(p.dbg & GEMM_DBG_NO_DMA)) {      // timing-only: dbg & 32 = no DMA at all, dbg & 8 = always K-tile 0 of the first tile (L2-resident operands)
+            const char* base = (p.dbg & GEMM_DBG_L2_OPERANDS) ? (ty >= 2 ? (const char*)p.A : (const char*)p.B) : (ty >= 2 ? a_base : b_base);
+            const uint32_t kb = (p.dbg & GEMM_DBG_L2_OPERANDS) ? 0u : (uint32_t)(d_kt * BK64 * 2);
             char* dst = smem + (d_par * 4 + ty) * 16384 + wrow_off;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
@@ -850,7 +848,7 @@ __device__ __forceinline__ void gemm_nt8p_bf16_kernel_body(GemmNtArgs p) {
     {                                                                                                                    \
         const uint32_t kbase = (uint32_t)c_par * 65536u;                                                                 \
         c_par ^= 1;                                                                                                      \
-        if (p.dbg & 4096) t_kt = __builtin_readcyclecounter();                                                           \
+        if (p.dbg & GEMM_DBG_KTILE_CYCLES) t_kt = __builtin_readcyclecounter();                                          \
         /* ---- phase 0: both B half-tiles + A row block 0 */                                                            \
         _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) fb0[kk] = P8_LDS(kbase + rb[kk]);                               \
         _Pragma("unroll") for (int kk = 0; kk < 4; ++kk) fb1[kk] = P8_LDS(kbase + 16384 + rb[kk]);                       \
@@ -876,13 +874,13 @@ __device__ __forceinline__ void gemm_nt8p_bf16_kernel_body(GemmNtArgs p) {
         else asm volatile("s_waitcnt vmcnt(6)" ::: "memory");                                                            \
         if ((KT) == nk - 1) epi.prefetch0(m0, n0);      /* behind the counted wait: ordinary loads in front of it would only tighten it */ \
         CMP(3)                                                                                                           \
-        if ((p.dbg & 4096) && ti > 0) {                                                                                  \
+        if ((p.dbg & GEMM_DBG_KTILE_CYCLES) && ti > 0) {                                                                 \
             _Pragma("unroll") for (int q = 0; q < 8; ++q)                                                                \
                 if (q == ((KT) < 8 ? (KT) : 7)) cyc_kt[q] += __builtin_readcyclecounter() - t_kt;                        \
         }                                                                                                                \
     }
 
-    long long cyc_main = 0, cyc_epi = 0, t_mark = (p.dbg & 16) ? __builtin_readcyclecounter() : 0;      // timing-only instrumentation (dbg & 16)
+    long long cyc_main = 0, cyc_epi = 0, t_mark = (p.dbg & GEMM_DBG_NT_CYCLES) ? __builtin_readcyclecounter() : 0;      // timing-only instrumentation (dbg & 16)
     long long cyc_kt[8] = {0, 0, 0, 0, 0, 0, 0, 0}, t_kt = 0;      // dbg & 4096: cycles by K-tile position inside a tile (first 8)
     f32x16 zero16;
 #pragma unroll
@@ -894,16 +892,16 @@ __device__ __forceinline__ void gemm_nt8p_bf16_kernel_body(GemmNtArgs p) {
 #pragma clang loop unroll(disable)
         for (int kt = 1; kt < nk; ++kt) P8_KTILE(P8_COMPUTE, kt)
         if (ti == my_tiles - 1 && wm == 0) __builtin_amdgcn_s_barrier();      // pairs with group 1's last barrier
-        if (p.dbg & 16) { const long long t = __builtin_readcyclecounter(); cyc_main += t - t_mark; t_mark = t; }
+        if (p.dbg & GEMM_DBG_NT_CYCLES) { const long long t = __builtin_readcyclecounter(); cyc_main += t - t_mark; t_mark = t; }
         epi.Es = smem + ((c_par ^ 1) * 4 + 2) * 16384 + wrow_off;
         eb = epi.run(acc, m0, n0);
-        if (p.dbg & 16) { const long long t = __builtin_readcyclecounter(); cyc_epi += t - t_mark; t_mark = t; }
+        if (p.dbg & GEMM_DBG_NT_CYCLES) { const long long t = __builtin_readcyclecounter(); cyc_epi += t - t_mark; t_mark = t; }
     }
-    if ((p.dbg & 4096) && tid == 0) {
+    if ((p.dbg & GEMM_DBG_KTILE_CYCLES) && tid == 0) {
 #pragma unroll
         for (int q = 0; q < 8; ++q) ((float*)p.C)[8192 + blockIdx.x * 8 + q] = (float)cyc_kt[q] / (float)(my_tiles > 1 ? my_tiles - 1 : 1);
     }
-    if ((p.dbg & 16) && tid == 0) {      // cycles per K-tile of the main loop, cycles per tile of the epilogue, into the first floats of C
+    if ((p.dbg & GEMM_DBG_NT_CYCLES) && tid == 0) {      // cycles per K-tile of the main loop, cycles per tile of the epilogue, into the first floats of C
         ((float*)p.C)[blockIdx.x * 2] = (float)cyc_main / (float)(my_tiles * nk);
         ((float*)p.C)[blockIdx.x * 2 + 1] = (float)cyc_epi / (float)my_tiles;
     }
@@ -928,42 +926,23 @@ static int launch_nt256_inst(const GemmNtArgs& p, int grid, hipStream_t stream) 
     const size_t lds = (size_t)NS64 * 512 * BK64 * 2 + 32768;   // 160 KiB
     return svla_launch<gemm_nt256k64_bf16_kernel<ACT, AUX, DROP>>(dim3(grid), dim3(NT256_THREADS), lds, stream, p);
 }
-// Kernel choice (measured, tools/ab_gemm.py, profiles/r03_nt_ab.txt): with the trimmed epilogue the 8-phase kernel wins on every shape of the
-// update (+2 ... +7 %); the 2-buffer kernel stays for N > 8192 (the LDS bias table) and as the A/B partner.  dbg bits 128 / 256 force the
-// 2-buffer / the 8-phase kernel.
-static inline bool nt_use_8p(const GemmNtArgs& p) {
-    if (p.N > 8192 || (p.dbg & 128)) return false;
-    return true;
-}
 // dropout is a compile-time flavour of the epilogue; instantiated for every (activation, operand) combination it can be requested with
 #define NT256_CASE(A_, X_)                                                                                                               \
-    return p.drop.thr ? (nt_use_8p(p) ? launch_nt8p_inst<A_, X_, true>(p, grid, stream) : launch_nt256_inst<A_, X_, true>(p, grid, stream))   \
-                      : (nt_use_8p(p) ? launch_nt8p_inst<A_, X_, false>(p, grid, stream) : launch_nt256_inst<A_, X_, false>(p, grid, stream))
-static int launch_nt256(const GemmNtArgs& p, int grid, hipStream_t stream) {
+    return p.drop.thr ? (p8 ? launch_nt8p_inst<A_, X_, true>(p, grid, stream) : launch_nt256_inst<A_, X_, true>(p, grid, stream))   \
+                      : (p8 ? launch_nt8p_inst<A_, X_, false>(p, grid, stream) : launch_nt256_inst<A_, X_, false>(p, grid, stream))
+static int launch_nt256(const GemmNtArgs& p, bool p8, int grid, hipStream_t stream) {      // p8: the 8-phase kernel (NT_8P), else the 2-buffer one
     const int aux = (p.residual ? 1 : 0) | (p.relu_mask ? 2 : 0);
-    if (p.bits_in) {
-        if (p.act != ACT_NONE) return SVLA_EINVAL;
-        NT256_CASE(0, 4);
-    }
+    if (p.bits_in) { if (p.act != ACT_NONE) return SVLA_EINVAL; NT256_CASE(0, 4); }
     switch (p.act * 4 + aux) {
-        case 0: NT256_CASE(0, 0);
-        case 1: NT256_CASE(0, 1);
-        case 2: NT256_CASE(0, 2);
-        case 3: NT256_CASE(0, 3);
-        case 4: NT256_CASE(1, 0);
-        case 5: NT256_CASE(1, 1);
-        case 6: NT256_CASE(1, 2);
-        case 7: NT256_CASE(1, 3);
-        case 8: NT256_CASE(2, 0);
-        case 9: NT256_CASE(2, 1);
-        case 10: NT256_CASE(2, 2);
-        case 11: NT256_CASE(2, 3);
+        case 0: NT256_CASE(0, 0);  case 1: NT256_CASE(0, 1);  case 2: NT256_CASE(0, 2);   case 3: NT256_CASE(0, 3);
+        case 4: NT256_CASE(1, 0);  case 5: NT256_CASE(1, 1);  case 6: NT256_CASE(1, 2);   case 7: NT256_CASE(1, 3);
+        case 8: NT256_CASE(2, 0);  case 9: NT256_CASE(2, 1);  case 10: NT256_CASE(2, 2);  case 11: NT256_CASE(2, 3);
         default: return SVLA_EINVAL;
     }
 }
 #undef NT256_CASE
 
-static int g_force_small_tile = 0, g_dbg = 0;
+static GemmKnobs& gemm_knobs() { static GemmKnobs k = gemm_knobs_from_env(); return k; }      // of this process; the environment is read once, at the first use
 // SVLA_GEMM_LOG=<file>: one line "kernel M N K" per big-GEMM launch, in launch order -- tools/prof_summarize.py joins it with the rocprofv3
 // counter rows of the same kernel names (i-th dispatch <-> i-th line), so HBM traffic is reported per (kernel, shape) and not as a launch-weighted mean
 static char g_last_kernel[96] = "";
@@ -971,13 +950,7 @@ static int g_last_shape[3] = {0, 0, 0};
 // extra = bytes per output row beyond the A and C rows (residual 2 N, sign bits N / 8): the profile summary counts them as algorithmic bytes;
 // to_file = false: remember the name only (the 128-tile kernel also runs the M % 256 tails, which are not logged, so its dispatches cannot be joined by index)
 static void gemm_log(const char* kernel, int M, int N, int K, int extra = 0, bool to_file = true) {
-    static FILE* f = nullptr;
-    static bool init = false;
-    if (!init) {
-        init = true;
-        const char* path = getenv("SVLA_GEMM_LOG");
-        if (path) f = fopen(path, "w");
-    }
+    static FILE* const f = [] { const char* path = getenv("SVLA_GEMM_LOG"); return path ? fopen(path, "w") : nullptr; }();
     snprintf(g_last_kernel, sizeof(g_last_kernel), "%s", kernel);
     g_last_shape[0] = M; g_last_shape[1] = N; g_last_shape[2] = K;
     static const bool log_all = getenv("SVLA_GEMM_LOG_ALL") != nullptr;      // shape studies (tools/): the 128-tile launches too -- such a log cannot be joined with counter rows
@@ -1006,25 +979,17 @@ static int gemm_globals_init() {
     });
     return g_gg.rc;
 }
-static int gemm_globals(hipStream_t stream, const GemmGlobals** out) {
-    if (!g_gg.n_cu) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return SVLA_EINVAL;
-        const int rc = gemm_globals_init();
-        if (rc) return rc;
-    }
-    *out = &g_gg;
-    return 0;
+static int gemm_globals(hipStream_t stream) {      // 0: g_gg is ready
+    if (g_gg.n_cu) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (stream && hipStreamIsCapturing(stream, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone) return SVLA_EINVAL;
+    return gemm_globals_init();
 }
-// on = 0/1/2: normal dispatch / force the 128x128 kernels / force the 256-tile kernels wherever their shape constraints hold (tests); on = 10 + f: flags f of the 256-tile kernels -- timing-only ablations 1 / 2 / 64,
-// 128 / 256 = force the 2-buffer kernel (gemm_nt256k64) / the 8-phase kernel (gemm_nt8p) (A/B comparisons)
+// on = 0/1/2 or 10 + GEMM_DBG_* bits (GemmKnobs, gemm_host.h); any value also initialises the dispatchers (without a device: SVLA_EINVAL, the knobs are set all the same)
 extern "C" int svla_gemm_force_small_tile(int on) {
-    if (gemm_globals_init()) return SVLA_EINVAL;
-    if (on >= 10) { g_dbg = on - 10; g_force_small_tile = 0; }
-    else { g_dbg = 0; g_force_small_tile = on; }
-    return SVLA_OK;
+    gemm_knobs_set(gemm_knobs(), on);
+    return gemm_globals_init() ? SVLA_EINVAL : SVLA_OK;
 }
-
 // the 128-tile kernel: one workgroup per 128 x 128 output tile, 66 KiB of LDS = max(NST operand stages 64 KiB, fp32 epilogue tile)
 static int launch_nt128(const GemmNtArgs& p, hipStream_t stream) {
     const int mt = (p.M + BM - 1) / BM, nt = p.N / BN;
@@ -1040,143 +1005,27 @@ static int nt_tail(const GemmNtArgs& p, size_t rows_done, hipStream_t stream) {
     if (p.residual) q.residual = p.residual + rows_done * p.ldr;
     if (p.bits_in) q.bits_in = p.bits_in + (rows_done >> 5) * (size_t)(p.N >> 6) * 256;
     if (p.bits_out) q.bits_out = p.bits_out + (rows_done >> 5) * (size_t)(p.N >> 6) * 256;
-    q.M = p.M - (int)rows_done;
-    q.row0 = (int)rows_done;
+    q.M = p.M - (int)rows_done; q.row0 = (int)rows_done;
     return launch_nt128(q, stream);
 }
-
-// ---- A-stationary assembly kernels (asmgen/nt_as_gen.py): K = 512, bf16 output, full 256-row panels; the M % 256 tail rows run as a
-// sub-problem on the 128-tile kernel (row0 keeps its dropout counters / sign-bit blocks on the global row index).
-#define NT_AS_NOT_TAKEN (-12345)
-// floor of the mid-M launch in 256-row panels (SVLA_NT_AS_MIN_PANELS: sweeps of tools/ab_midm.py; the cost model below decides above it)
-static int nt_as_min_panels() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("SVLA_NT_AS_MIN_PANELS"); v = e ? atoi(e) : 8; }
-    return v;
-}
-static int nt_as_try(const GemmNtArgs& p, hipStream_t stream) {
-    if ((p.K != 512 && p.K != 384) || p.out_f32 || (p.N % 128) || p.N > 4096 || p.N < 128 || (p.dbg & 8192) || g_force_small_tile == 1) return NT_AS_NOT_TAKEN;
-    if (p.relu_mask) return NT_AS_NOT_TAKEN;
-    const int npanels = p.M / 256;
-    // >= 2 panels per CU: the row-streaming launch (one persistent workgroup per CU, phases); fewer: the mid-M launch below
-    if (npanels < nt_as_min_panels() && g_force_small_tile != 2) return NT_AS_NOT_TAKEN;
-    if (npanels < 1) return NT_AS_NOT_TAKEN;
-    const char* name = nullptr;
-    if (p.residual) return NT_AS_NOT_TAKEN;
-    if (p.bits_in) {      // input gradient under the ReLU sign bits (+ dropout scale as alpha): no bias
-        if (p.act == ACT_NONE && !p.bias && !p.drop.thr && !p.bits_out) name = "svla_nt_as_f3";
-    } else if (p.act == ACT_RELU && p.bits_out && p.alpha == 1.f) {
-        // the dropout counter of the assembly kernel is 32 bits wide: element pairs of the whole logical tensor must fit
-        if (!p.drop.thr) name = "svla_nt_as_f1";
-        else if ((unsigned long long)p.M * (unsigned long long)p.drop.row_mult * (unsigned long long)p.N / 2 < 0xffffffffull) name = "svla_nt_as_f1d";
-    } else if (p.act == ACT_NONE && !p.bits_out && !p.drop.thr && p.alpha == 1.f) name = "svla_nt_as_f0";
-    if (p.K == 384) {      // the ViT-S / DINOv2-feature width: bias (qkv), bias + erf-GELU (fc1), bias + ReLU + sign bits (the policy's visual compressor)
-        if (name && !strcmp(name, "svla_nt_as_f0")) name = "svla_nt_as_k384_f0";
-        else if (name && !strcmp(name, "svla_nt_as_f1")) name = "svla_nt_as_k384_f1";
-        else if (!p.bits_in && p.act == ACT_GELU && !p.bits_out && !p.drop.thr && p.alpha == 1.f) name = "svla_nt_as_k384_f2";
-        else name = nullptr;
-    }
-#ifdef SVLA_ASM_DEBUG      // instrumented builds of tools/ only (SVLA_EXTRA_FLAGS=-DSVLA_ASM_DEBUG): svla_nt_as_f0_<variant>
-    static char dbg_name[96];
-    if (name && getenv("SVLA_NT_AS_VARIANT")) {
-        snprintf(dbg_name, sizeof(dbg_name), "%s_%s", name, getenv("SVLA_NT_AS_VARIANT"));
-        name = dbg_name;
-    }
-#endif
-    if (!name || !svla_asm_has(name)) return NT_AS_NOT_TAKEN;
-    // the sign-bit offset of a panel (panel * N * 32 bytes) is 32-bit scalar arithmetic in the kernel (asmgen/nt_as_gen.py bits_srd)
-    if ((p.bits_in || p.bits_out) && (unsigned long long)p.M * (unsigned long long)p.N / 8 >= 0xffffffffull) return NT_AS_NOT_TAKEN;
-    const GemmGlobals* gg = nullptr;
-    { const int rc = gemm_globals(stream, &gg); if (rc) return rc; }
-    const int n_cu = gg->n_cu;
-    float* const zero_bias = gg->zero_bias;
-    NtAsKarg k;
-    memset(&k, 0, sizeof(k));
-    k.A = p.A; k.lda = p.lda; k.B = p.B; k.ldb = p.ldb; k.bias = p.bias ? p.bias : zero_bias; k.C = p.C; k.ldc = p.ldc;
-    {      // phase spread over workgroups: (workgroup & cmask) < NS/4 extra steps, cmask + 1 = the largest power of two <= NS/4
-        int q = p.N / 256, m = 1;
-        while (m * 2 <= q) m *= 2;
-        k.cmask = q >= 1 ? m - 1 : 0;
-    }
-    k.N = p.N; k.alpha = p.alpha; k.npanels = npanels; k.bits = p.bits_in ? (const void*)p.bits_in : (const void*)p.bits_out;
+// the A-stationary assembly kernels (asmgen/nt_as_gen.py; nt_as_plan): the plan's whole panels
+static int launch_nt_as(const GemmNtArgs& p, const NtPlan& pl, hipStream_t stream) {
+    NtAsKarg k; memset(&k, 0, sizeof(k));
+    k.A = p.A; k.lda = p.lda; k.B = p.B; k.ldb = p.ldb; k.bias = p.bias ? p.bias : g_gg.zero_bias; k.C = p.C; k.ldc = p.ldc;
+    k.N = p.N; k.alpha = p.alpha; k.npanels = pl.main_rows / 256; k.bits = p.bits_in ? (const void*)p.bits_in : (const void*)p.bits_out;
     k.key = p.drop.key; k.thr = p.drop.thr; k.scale = p.drop.scale; k.row_mult = p.drop.row_mult; k.seed_dev = p.drop.seed_dev; k.stream_key = p.drop.stream_key;
-    k.nr = p.N; k.flags = 0;
-    k.grid = npanels < n_cu ? npanels : n_cu;
-    int grid_y = 1;
-    if (npanels < 2 * n_cu) {
-        // mid-M (an acting step's 45 panels, the 233 of the batch-256 probe, the ViT's 216): too few panels to give every CU two sweeps.  The grid becomes
-        // (panel slots) x (n-ranges): workgroup (x, y) sweeps columns [y nr, (y + 1) nr) of panels x, x + slots, ...; no phases (a workgroup that holds one
-        // panel has nothing to de-phase).  nsplit minimises rounds * (steps per sweep + ~2.5 steps of prologue / drain) over the divisors of N / 128.
-        // Cost model, calibrated on profiles/r05_midm_sweep.txt (asm side within ~10 % of the measurements): one n-step (64 columns of a 256-row panel) takes
-        // ~2.76 us * K/512; a workgroup pays ~5 steps per panel it loads (the fragment-shaped A gather runs at ~13 B/clk) + its sweep; the tile kernels take
-        // ~(6.2 + 11.6 K/512) us per round of 256 tiles.  The assembly launch is taken when it is at least 5 % ahead (a ragged M adds the tail launch).
-        const int ns = p.N / 64;
-        double best = 1e30;
-        int best_d = 1, best_slots = k.grid;
-        for (int d = 1; d <= p.N / 128; ++d) {
-            if ((p.N / 128) % d) continue;
-            int slots = npanels * d <= n_cu ? npanels : n_cu / d;
-            if (slots < 1) break;
-            const int rounds = (npanels + slots - 1) / slots;
-            const double cost = rounds * ((double)ns / d + 5.0);
-            if (cost < best - 1e-9) { best = cost; best_d = d; best_slots = slots; }
-        }
-        if (g_force_small_tile != 2) {
-            const long tiles = (long)((p.M + 255) / 256) * ((p.N + 255) / 256);
-            const double hip = (double)((tiles + n_cu - 1) / n_cu) * (6.2 + 11.6 * p.K / 512.0);
-            const double asm_cost = best * 2.76 * p.K / 512.0 + ((p.M % 256) ? 15.0 : 0.0);      // a ragged M: + the tail launch behind it (~15 us in a stream, r05_vit_kernel_stats.txt)
-            if (asm_cost > 0.95 * hip) return NT_AS_NOT_TAKEN;
-        }
-        grid_y = best_d;
-        k.grid = best_slots;
-        k.nr = p.N / best_d;
-        k.flags = 1;
-        k.cmask = 0;
-    }
+    k.grid = pl.grid_x; k.nr = pl.nr; k.flags = pl.flags; k.cmask = pl.cmask;
 #ifdef SVLA_ASM_DEBUG
     if (getenv("SVLA_NT_AS_DBGBUF")) k.bits = (const void*)strtoull(getenv("SVLA_NT_AS_DBGBUF"), nullptr, 16);      // timing builds of tools/time_nt_as.py
 #endif
-    gemm_log(name, npanels * 256, p.N, p.K, (p.bits_in || p.bits_out) ? p.N / 8 : 0);
-    const int rc = svla_asm_launch2(name, &k, sizeof(k), k.grid, grid_y, 256, stream);
-    if (rc) return rc;
-    return p.M > npanels * 256 ? nt_tail(p, (size_t)npanels * 256, stream) : SVLA_OK;
+    return svla_asm_launch2(pl.kernel, &k, sizeof(k), pl.grid_x, pl.grid_y, 256, stream);
 }
-
-// ---- output-stationary assembly kernels (asmgen/nt_os_gen.py): K > 512 (or K = 512 with a residual), bias / residual epilogues without dropout, N % 256 == 0,
-// K % 128 == 0, full 256-row tiles; the M % 256 tail rows run on the 128-tile kernel.  g_dbg & 16384 = off (A/B: tools/ab_nt_os.py).
-static int nt_os_try(const GemmNtArgs& p, hipStream_t stream) {
-    if (p.out_f32 || (p.N % 256) || p.N > 4096 || (p.K % 128) || p.K < 384 || (p.dbg & (8192 | 16384)) || g_force_small_tile == 1) return NT_AS_NOT_TAKEN;
-    if (p.relu_mask || p.bits_in || p.bits_out || p.drop.thr || p.act != ACT_NONE || p.alpha != 1.f) return NT_AS_NOT_TAKEN;
-    const int mtiles = p.M / 256, ntn = p.N / 256;
-    if ((long)mtiles * ntn < 1024 && g_force_small_tile != 2) return NT_AS_NOT_TAKEN;      // fewer than four tiles per CU: the two-workgroup-per-CU tile kernel balances better
-    if (mtiles < 1) return NT_AS_NOT_TAKEN;
-    const char* name = p.bias ? (p.residual ? "svla_nt_os_br" : "svla_nt_os_b") : (p.residual ? "svla_nt_os_r" : "svla_nt_os_p");
-#ifdef SVLA_ASM_DEBUG      // timing-only builds of tools/var_nt_os.py: svla_nt_os_r_<variant>
-    static char dbg_name[96];
-    if (getenv("SVLA_NT_OS_VARIANT")) {
-        snprintf(dbg_name, sizeof(dbg_name), "%s_%s", name, getenv("SVLA_NT_OS_VARIANT"));
-        name = dbg_name;
-    }
-#endif
-    if (!svla_asm_has(name)) return NT_AS_NOT_TAKEN;
-    const GemmGlobals* gg = nullptr;
-    { const int rc = gemm_globals(stream, &gg); if (rc) return rc; }
-    const int n_cu = gg->n_cu;
-    NtOsKarg k;
-    memset(&k, 0, sizeof(k));
+// the output-stationary assembly kernels (asmgen/nt_os_gen.py; nt_os_plan): the plan's whole 256-row tiles
+static int launch_nt_os(const GemmNtArgs& p, const NtPlan& pl, hipStream_t stream) {
+    NtOsKarg k; memset(&k, 0, sizeof(k));
     k.A = p.A; k.lda = p.lda; k.B = p.B; k.ldb = p.ldb; k.bias = p.bias; k.res = p.residual; k.ldr = p.ldr; k.C = p.C; k.ldc = p.ldc;
-    k.M = mtiles * 256; k.N = p.N; k.K = p.K; k.ntn = ntn; k.ntiles = mtiles * ntn; k.grid = k.ntiles < n_cu ? k.ntiles : n_cu;
-    gemm_log(name, k.M, p.N, p.K, p.residual ? 2 * p.N : 0);
-    const int rc = svla_asm_launch(name, &k, sizeof(k), k.grid, 256, stream);
-    if (rc) return rc;
-    return p.M > mtiles * 256 ? nt_tail(p, (size_t)mtiles * 256, stream) : SVLA_OK;
-}
-
-// fewest 256x256 tiles for which the 256-tile kernel is chosen over the 128-tile one (SVLA_NT256_MIN_TILES: sweep of tools/acting_force_probe.py)
-static int nt256_min_tiles() {
-    static int v = 0;
-    if (!v) { const char* e = getenv("SVLA_NT256_MIN_TILES"); v = e ? atoi(e) : 160; }
-    return v;
+    k.M = pl.main_rows; k.N = p.N; k.K = p.K; k.ntn = p.N / 256; k.ntiles = pl.main_rows / 256 * k.ntn; k.grid = pl.grid_x;
+    return svla_asm_launch(pl.kernel, &k, sizeof(k), pl.grid_x, 256, stream);
 }
 
 extern "C" int svla_gemm_nt_bf16(const bf16_t* A, long lda, const bf16_t* B, long ldb, const float* bias,
@@ -1187,30 +1036,36 @@ extern "C" int svla_gemm_nt_bf16(const bf16_t* A, long lda, const bf16_t* B, lon
     if ((relu_bits && (relu_mask || residual || out_f32)) || (relu_bits_out && (act != ACT_RELU || out_f32 || residual || relu_mask || relu_bits))) return SVLA_EINVAL;
     if (act < ACT_NONE || act > ACT_GELU) return SVLA_EINVAL;
     if ((lda % 8) || (ldb % 8) || (ldc % (out_f32 ? 4 : 8)) || (residual && (ldr % 8)) || (relu_mask && (ldm % 8))) return SVLA_EINVAL;
-    GemmNtArgs p{A, lda, B, ldb, bias, residual, ldr, relu_mask, ldm, C, ldc, M, N, K, act, out_f32, alpha, relu_bits_out, relu_bits, drop_cfg(drop), 0, g_dbg, 0.f};
-    {
-        const int rc = nt_as_try(p, (hipStream_t)stream);      // K = 512 row-streaming GEMMs: the A-stationary assembly kernels
-        if (rc != NT_AS_NOT_TAKEN) return rc;
+    const GemmKnobs& kn = gemm_knobs();
+    const GemmNtArgs p{A, lda, B, ldb, bias, residual, ldr, relu_mask, ldm, C, ldc, M, N, K, act, out_f32, alpha, relu_bits_out, relu_bits, drop_cfg(drop), 0, kn.dbg, 0.f};
+    const NtProblem q{M, N, K, act, out_f32 != 0, alpha == 1.f, bias != nullptr, residual != nullptr, relu_mask != nullptr, relu_bits != nullptr, relu_bits_out != nullptr,
+                      p.drop.thr != 0, p.drop.row_mult};
+    const int n_cu = svla_cu_count();
+    const NtPlan pl = nt_plan(q, kn, n_cu, svla_asm_has);
+    const hipStream_t s = (hipStream_t)stream;
+    if (pl.path == NT_AS || pl.path == NT_OS) { const int rc = gemm_globals(s); if (rc) return rc; }      // only in front of an assembly launch
+    else if (pl.path != NT_128 && !n_cu) return (int)hipErrorInvalidDevice;
+    gemm_log(pl.kernel, pl.main_rows, N, K, pl.log_extra, pl.log_joinable);
+    int rc = SVLA_EINVAL;
+    switch (pl.path) {
+        case NT_AS: rc = launch_nt_as(p, pl, s); break;
+        case NT_OS: rc = launch_nt_os(p, pl, s); break;
+        case NT_8P: case NT_2BUF: rc = launch_nt256(p, pl.path == NT_8P, pl.grid_x, s); break;
+        case NT_128: rc = launch_nt128(p, s); break;
     }
-    {
-        const int rc = nt_os_try(p, (hipStream_t)stream);      // K > 512 without dropout: the output-stationary assembly kernels
-        if (rc != NT_AS_NOT_TAKEN) return rc;
-    }
-    // N % 256 == 128 with N >= 384 (the ViT-S widths 384 and 1152): the last n-tile is a half tile (75 % / 90 % of the MFMA work useful) --
-    // still well ahead of the 128-tile kernel
-    if (!out_f32 && ((N % 256) == 0 || ((N % 128) == 0 && N >= 384)) && (K % BK64) == 0 && K >= 2 * BK64 && ((long)((M + 255) / 256) * ((N + 255) / 256) >= nt256_min_tiles() || g_force_small_tile == 2) && g_force_small_tile != 1) {
-        int n_cu = svla_cu_count();
-        if (!n_cu) return (int)hipErrorInvalidDevice;
-        n_cu = (n_cu / 8) * 8;
-        if (n_cu < 8) n_cu = 8;
-        const int ntiles = ((M + 255) / 256) * ((N + 255) / 256);
-        gemm_log(nt_use_8p(p) ? "gemm_nt8p_bf16_kernel" : "gemm_nt256k64_bf16_kernel", M, N, K, (p.residual ? 2 * N : 0) + ((p.bits_in || p.bits_out) ? N / 8 : 0) + (p.relu_mask ? 2 * N : 0));
-        int grid = n_cu;                       // persistent: one 512-thread workgroup (160 KiB LDS) per CU
-        while (grid > 8 && (grid / 8) * 8 > ntiles) grid -= 8;
-        return launch_nt256(p, grid, (hipStream_t)stream);
-    }
-    gemm_log("gemm_nt_bf16_kernel", M, N, K, 0, false);
-    return launch_nt128(p, (hipStream_t)stream);
+    if (rc || !pl.tail_rows) return rc;
+    return nt_tail(p, (size_t)pl.main_rows, s);      // the M % 256 rows behind either assembly family: the 128-tile kernel
+}
+// The plan svla_gemm_nt_bf16 would launch from, with this process's knobs and every assembly kernel present; no HIP call (include/svla.h: the out[] layout)
+extern "C" int svla_gemm_nt_plan(int M, int N, int K, int act, int out_f32, int epilogue, float alpha, int drop_on, int row_mult, int n_cu, char* kernel, int cap, int* out) {
+    const NtProblem q{M, N, K, act, out_f32 != 0, alpha == 1.f, (epilogue & 1) != 0, (epilogue & 2) != 0, (epilogue & 4) != 0, (epilogue & 8) != 0, (epilogue & 16) != 0,
+                      drop_on != 0, row_mult > 0 ? row_mult : 1};
+    if (M <= 0 || N <= 0 || K <= 0 || (N % BN) || (K % BK) || act < ACT_NONE || act > ACT_GELU || n_cu <= 0 || !kernel || cap <= 0 || !out) return SVLA_EINVAL;
+    const NtPlan pl = nt_plan(q, gemm_knobs(), n_cu, [](const char*) { return 1; });
+    snprintf(kernel, (size_t)cap, "%s", pl.kernel);
+    const int v[10] = {pl.path, pl.main_rows, pl.tail_rows, pl.grid_x, pl.grid_y, pl.nr, pl.flags, pl.cmask, pl.log_extra, pl.log_joinable};
+    memcpy(out, v, sizeof(v));
+    return SVLA_OK;
 }
 
 // RMSNorm(A) . W^T for small M (the frozen T5 encoder's and the llama decoder's pre-norm linears in an acting step: M = 64 ... 768 rows, where the norm was a
@@ -1501,9 +1356,9 @@ __global__ void __launch_bounds__(NT256_THREADS, 2) gemm_tn8p_bf16_kernel(GemmTn
     const int wrow_off = __builtin_amdgcn_readfirstlane(wid * 1024);
     int dq = 0;
     auto issue = [&]() {
-        if (dq < nph && !(p.dbg & 32)) {
+        if (dq < nph && !(p.dbg & GEMM_DBG_NO_DMA)) {
             char* dst = smem + (dq & 7) * 16384 + wrow_off;
-            if (p.dbg & 16) {
+            if (p.dbg & GEMM_DBG_TN_NT_LOADS) {
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ybase + offy),
                                                  (__attribute__((address_space(3))) void*)dst, 16, 0, 2);
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xbase + offx),
@@ -1514,7 +1369,7 @@ __global__ void __launch_bounds__(NT256_THREADS, 2) gemm_tn8p_bf16_kernel(GemmTn
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(xbase + offx),
                                              (__attribute__((address_space(3))) void*)(dst + 8192), 16, 0, 0);
             }
-            if (!(p.dbg & 8)) {      // timing-only (8): re-read the same 16 rows (operands served by the L2)
+            if (!(p.dbg & GEMM_DBG_L2_OPERANDS)) {      // timing-only (8): re-read the same 16 rows (operands served by the L2)
                 ybase += ystep;
                 xbase += xstep;
             }
@@ -1557,7 +1412,7 @@ __global__ void __launch_bounds__(NT256_THREADS, 2) gemm_tn8p_bf16_kernel(GemmTn
     if (nph > TNP_L) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
-    const long long t_begin = (p.dbg & 4) ? __builtin_readcyclecounter() : 0;
+    const long long t_begin = (p.dbg & GEMM_DBG_PHASE_CYCLES) ? __builtin_readcyclecounter() : 0;
     // Transposed fragment gathers from inline asm: behind the builtin, hipcc cannot tell the reads from the LDS-DMA writes still in
     // flight and drains the whole DMA queue (s_waitcnt vmcnt(0)) in front of the first one.  Rows r0 and r0 + 4 (+ 4 * 512 B).
     // ONE barrier per phase, two fragment register sets: phase P = [step P's fragments retire] [gather step P+1 (its slot was published
@@ -1597,7 +1452,7 @@ __global__ void __launch_bounds__(NT256_THREADS, 2) gemm_tn8p_bf16_kernel(GemmTn
         asm volatile("s_barrier"                                                                                                              \
                      : "+v"(acc[0][0]), "+v"(acc[0][1]), "+v"(acc[1][0]), "+v"(acc[1][1]), "+v"(acc[2][0]), "+v"(acc[2][1]), "+v"(acc[3][0]), "+v"(acc[3][1]), "+v"(accb)::"memory"); \
     }
-    if (p.dbg & 64) {        // timing-only: DMA stream + barriers alone
+    if (p.dbg & GEMM_DBG_DMA_ONLY) {        // timing-only: DMA stream + barriers alone
         for (int ph = 0; ph < nph; ++ph) {
             issue();
             if (dq <= nph) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -1616,7 +1471,7 @@ __global__ void __launch_bounds__(NT256_THREADS, 2) gemm_tn8p_bf16_kernel(GemmTn
     }
 #undef TNP_PHASE
 #undef TNP_READS
-    if (p.dbg & 4) {      // timing-only: shader cycles per phase of this workgroup instead of the gradient
+    if (p.dbg & GEMM_DBG_PHASE_CYCLES) {      // timing-only: shader cycles per phase of this workgroup instead of the gradient
         if (tid == 0) p.dW[blockIdx.x] = (float)(__builtin_readcyclecounter() - t_begin) / (float)nph;
         return;
     }
@@ -1638,55 +1493,46 @@ __global__ void __launch_bounds__(NT256_THREADS, 2) gemm_tn8p_bf16_kernel(GemmTn
     }
 }
 
-// force = 0 / 1 / 2: as svla_gemm_force_small_tile
-static int gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* dW, long ldw, float* db, int M, int N, int K, int force, void* stream) {
-    if (force == 2 && (N % 256) == 0 && (K % 256) == 0 && M >= 2 * TN256_ROWS && (M % TN256_ROWS) != 0) {
-        // forced big-tile mode (tests: the reference goldens through the kernels that carry the update): whole 64-row groups on the 256-tile
-        // kernel, the ragged tail on the small one
-        const int mb = M / TN256_ROWS * TN256_ROWS;
-        const int rc = gemm_tn_f32acc(dY, ldy, X, ldx, dW, ldw, db, mb, N, K, 2, stream);
-        if (rc) return rc;
-        return gemm_tn_f32acc(dY + (size_t)mb * ldy, ldy, X + (size_t)mb * ldx, ldx, dW, ldw, db, M - mb, N, K, 1, stream);
+static_assert(BN == 128 && BK == 32 && TN256_ROWS == TN_GROUP_ROWS && TK == 64, "gemm_host.h restates these tile sizes");
+// one part of a TnPlan (tn_part); gemm_tn_bf16_kernel and gemm_tn256_bf16_kernel are launched without a record
+static int launch_tn_part(const TnPart& t, const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* dW, long ldw, float* db, int N, int K, hipStream_t stream) {
+    if (t.recorded) gemm_log(t.kernel, t.rows, N, K);
+    if (t.path == TN_128) {
+        if (t.colsum) { const int rc = svla_colsum_bf16(dY, ldy, t.rows, N, 1, db, stream); if (rc) return rc; }   // small-tile path: bias gradient as a separate column-sum pass
+        GemmTnArgs p{dY, ldy, X, ldx, dW, ldw, t.rows, N, K, t.chunk_rows, g_svla_det};
+        const size_t lds = 2 * 2 * TK * 128 * sizeof(bf16_t);  // 64 KiB
+        return svla_launch<gemm_tn_bf16_kernel>(dim3(t.grid), dim3(NTHREADS), lds, stream, p);
     }
-    if ((N % 256) == 0 && (K % 256) == 0 && (M % TN256_ROWS) == 0 && (M >= 16384 || (M >= 8192 && (long)N * K >= 1024L * 512) || force == 2) && force != 1) {
-        // measured (r03): at 16 k rows the 256-tile kernel is 1.0x (512 x 512) to 2.0x (1536 x 512) the 128-tile one, at 8 k rows 0.7x / 1.2-1.9x
+    if (t.path == TN_OS) {
         const int ntile256 = (N / 256) * (K / 256);
-        int chunks = 256 / ntile256;                                  // <= one workgroup per CU (no second dispatch wave)
-        if (chunks < 1) chunks = 1;
-        int chunk_rows = ((M + chunks - 1) / chunks + TN256_ROWS - 1) / TN256_ROWS * TN256_ROWS;
-        chunks = (M + chunk_rows - 1) / chunk_rows;
-        GemmTn256Args q{dY, ldy, X, ldx, dW, ldw, db, M, N, K, chunk_rows, g_dbg, g_svla_det};
-        const size_t lds256 = (size_t)TN_NS * 2 * TN256_ROWS * 256 * sizeof(bf16_t);   // 128 KiB
-        if (!(g_dbg & (128 | 8192)) && !g_svla_det.i64[0] && !g_svla_det.i64[1] && svla_asm_has("svla_tn_os")) {
-            // output-stationary assembly kernel (asmgen/tn_os_gen.py): 4 waves x 128 x 128 accumulators, 4-slot LDS-DMA ring
-            TnOsKarg k = {dY, ldy, X, ldx, dW, ldw, db, M, N, K, chunk_rows, ntile256, K / 256, ntile256 * chunks};
-            gemm_log("svla_tn_os", M, N, K);
-            return svla_asm_launch("svla_tn_os", &k, sizeof(k), ntile256 * chunks, 256, (hipStream_t)stream);
-        }
-        if (!(g_dbg & 128)) {
-            gemm_log("gemm_tn8p_bf16_kernel", M, N, K);
-            return svla_launch<gemm_tn8p_bf16_kernel>(dim3(ntile256 * chunks), dim3(NT256_THREADS), lds256, (hipStream_t)stream, q);
-        }
-        return svla_launch<gemm_tn256_bf16_kernel>(dim3(ntile256 * chunks), dim3(NT256_THREADS), lds256, (hipStream_t)stream, q);
+        TnOsKarg k = {dY, ldy, X, ldx, dW, ldw, db, t.rows, N, K, t.chunk_rows, ntile256, K / 256, t.grid};
+        return svla_asm_launch(t.kernel, &k, sizeof(k), t.grid, 256, stream);
     }
-    if (db) {   // small-tile path: bias gradient as a separate column-sum pass
-        const int rc = svla_colsum_bf16(dY, ldy, M, N, 1, db, stream);
-        if (rc) return rc;
-    }
-    const int ntile = (N / 128) * (K / 128);
-    // aim for ~2048 workgroups; chunk is a multiple of the 64-row reduction tile
-    int chunks = (2048 + ntile - 1) / ntile;
-    int chunk_rows = ((M + chunks - 1) / chunks + TK - 1) / TK * TK;
-    if (chunk_rows < 4 * TK) chunk_rows = 4 * TK;
-    chunks = (M + chunk_rows - 1) / chunk_rows;
-    GemmTnArgs p{dY, ldy, X, ldx, dW, ldw, M, N, K, chunk_rows, g_svla_det};
-    const size_t lds = 2 * 2 * TK * 128 * sizeof(bf16_t);  // 64 KiB
-    return svla_launch<gemm_tn_bf16_kernel>(dim3(ntile * chunks), dim3(NTHREADS), lds, (hipStream_t)stream, p);
+    GemmTn256Args q{dY, ldy, X, ldx, dW, ldw, db, t.rows, N, K, t.chunk_rows, gemm_knobs().dbg, g_svla_det};
+    const size_t lds256 = (size_t)TN_NS * 2 * TN256_ROWS * 256 * sizeof(bf16_t);   // 128 KiB
+    if (t.path == TN_8P) return svla_launch<gemm_tn8p_bf16_kernel>(dim3(t.grid), dim3(NT256_THREADS), lds256, stream, q);
+    return svla_launch<gemm_tn256_bf16_kernel>(dim3(t.grid), dim3(NT256_THREADS), lds256, stream, q);
 }
 extern "C" int svla_gemm_tn_f32acc(const bf16_t* dY, long ldy, const bf16_t* X, long ldx, float* dW, long ldw, float* db, int M,
                                    int N, int K, void* stream) {
     if (M <= 0 || (N % 128) || (K % 128) || (ldy % 8) || (ldx % 8)) return SVLA_EINVAL;
-    return gemm_tn_f32acc(dY, ldy, X, ldx, dW, ldw, db, M, N, K, g_force_small_tile, stream);
+    const TnPlan pl = tn_plan(M, N, K, db != nullptr, gemm_knobs(), g_svla_det.i64[0] || g_svla_det.i64[1], svla_asm_has);
+    const int rc = launch_tn_part(pl.main, dY, ldy, X, ldx, dW, ldw, db, N, K, (hipStream_t)stream);
+    if (rc || !pl.tail.rows) return rc;
+    const size_t mb = (size_t)pl.main.rows;
+    return launch_tn_part(pl.tail, dY + mb * ldy, ldy, X + mb * ldx, ldx, dW, ldw, db, N, K, (hipStream_t)stream);
+}
+// The plan svla_gemm_tn_f32acc would launch from, with this process's knobs and svla_tn_os present; no HIP call (include/svla.h: the out[] layout)
+extern "C" int svla_gemm_tn_plan(int M, int N, int K, int has_db, int det_on, int n_cu, char* kernel, int cap, int* out) {
+    if (M <= 0 || N <= 0 || K <= 0 || (N % 128) || (K % 128) || n_cu <= 0 || !kernel || cap <= 0 || !out) return SVLA_EINVAL;
+    const TnPlan pl = tn_plan(M, N, K, has_db != 0, gemm_knobs(), det_on != 0, [](const char*) { return 1; });
+    snprintf(kernel, (size_t)cap, "%s%s%s", pl.main.kernel, pl.tail.rows ? "+" : "", pl.tail.rows ? pl.tail.kernel : "");
+    const TnPart* part[2] = {&pl.main, &pl.tail};
+    for (int i = 0; i < 2; ++i) {
+        const int v[6] = {part[i]->path, part[i]->rows, part[i]->chunk_rows, part[i]->grid, part[i]->colsum, part[i]->recorded};
+        memcpy(out + 6 * i, v, sizeof(v));
+    }
+    return SVLA_OK;
 }
 
 // Column sums (bias gradients): db[n] += sum_m dY[m, n].  HBM-bound single pass, 16-byte loads.

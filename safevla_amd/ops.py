@@ -381,6 +381,27 @@ def gemm_last_kernel():
     return buf.value.decode(), tuple(mnk)
 
 
+def _gemm_plan(entry, n_out, *scalars):
+    import ctypes
+
+    buf, out = ctypes.create_string_buffer(96), (ctypes.c_int * n_out)()
+    lib().call(entry, *scalars, ctypes.cast(buf, ctypes.c_void_p), 96, ctypes.cast(out, ctypes.c_void_p))
+    return buf.value.decode(), tuple(out)
+
+
+def gemm_nt_plan(M, N, K, n_cu, act=0, out_f32=False, bias=False, residual=False, relu_mask=False, relu_bits=False, relu_bits_out=False, alpha=1.0,
+                 drop=False, row_mult=1):
+    """(kernel, (path, main rows, tail rows, grid_x, grid_y, nr, flags, cmask, log extra, log joinable)): what gemm_nt would launch on n_cu compute units
+    under the current gemm_force_small_tile hook (svla_gemm_nt_plan; no GPU needed)."""
+    epi = bool(bias) | bool(residual) << 1 | bool(relu_mask) << 2 | bool(relu_bits) << 3 | bool(relu_bits_out) << 4
+    return _gemm_plan("svla_gemm_nt_plan", 10, M, N, K, int(act), int(out_f32), epi, float(alpha), int(bool(drop)), int(row_mult), int(n_cu))
+
+
+def gemm_tn_plan(M, N, K, n_cu, db=True, det=False):
+    """("main" or "main+tail" kernel, 2 x (path, rows, chunk_rows, grid, colsum, recorded)): what gemm_tn_acc would launch (svla_gemm_tn_plan; no GPU needed)."""
+    return _gemm_plan("svla_gemm_tn_plan", 12, M, N, K, int(bool(db)), int(bool(det)), int(n_cu))
+
+
 def attn_bwd_two_pass(on) -> None:
     """True: the dQ + dK/dV kernel pair instead of the single-pass attention backward (A/B and tests)."""
     lib().call("svla_attn_bwd_two_pass", int(bool(on)))

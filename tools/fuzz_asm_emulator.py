@@ -56,7 +56,7 @@ def main():
         panels = rng.choice([1, 1, 2, 3])
         N = rng.choice([256, 384, 512, 640, 768, 1024] if not fl.startswith("k384") else [256, 384, 512, 768, 1152])
         if fl in ("f1", "f1d", "f3", "k384_f1") and N % 256:
-            N = N // 256 * 256 or 256                   # the sign-bit flavours are dispatched at N % 256 == 0 (csrc/gemm.hip nt_as_try)
+            N = N // 256 * 256 or 256                   # the sign-bit flavours are dispatched at N % 256 == 0 (csrc/gemm_host.h nt_as_plan)
         mid = rng.random() < 0.45
         nsplit = rng.choice([d for d in (1, 2, 3, 4) if (N // 128) % d == 0 and (N // d) % 128 == 0]) if mid else 1
         grid = rng.randint(1, panels)
