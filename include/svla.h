@@ -323,6 +323,21 @@ int svla_zero_bytes(void* p, long bytes, void* stream);
  * recorded launch sequence of the step does not depend on the step counter. */
 int svla_kv_append_bf16(const svla_bf16* src, long ld_src, svla_bf16* cache, long cache_rows, int width, const int64_t* t_dev, int B,
                         void* stream);
+/* The same append with a cache row and a slot PER ROW (llama/model.py:279-293, cache_k[:bsz, start_pos] = xk, for a vector of episodes that start, end and stall
+ * independently): cache[cache_row[r], pos[r], 0:width] = src[r*ld_src + 0:width] for r < rows.  cache holds cache_rows token rows per cache row.  cache_row: int32
+ * [rows] or NULL (identity); pos: int32 [rows]; pos[r] < 0 skips the row (so does a slot >= cache_rows or a negative cache row).  Both arrays are read from device
+ * memory, so the call's arguments do not depend on the step.  width, ld_src multiples of 8. */
+int svla_kv_append_rows_bf16(const svla_bf16* src, long ld_src, svla_bf16* cache, long cache_rows, int width, const int* cache_row, const int* pos, int rows,
+                             void* stream);
+/* Single-query attention of that vector step (llama/model.py:295-322: scores of the new token against cache_k / cache_v[:bsz, : start_pos + seqlen], softmax, P V;
+ * no RoPE in this decoder and the time encoding is added to the input, so one query is invariant to key order): row r reads keys [0, min(klen[r], kv_rows)) of cache
+ * row cache_row[r] (NULL: r), kv_rows token rows per cache row, 1 <= kv_rows <= 1024.  With slot t mod W written at step t and klen = min(t + 1, W) the ring is the
+ * sliding window over the last W embedded steps of early_fusion_tsfm_models.py:491-497.  Q row r at Q + r*ldq, K / V token rows ld apart, O [rows, ldo], LSE
+ * [rows, H] (natural log) or NULL.  head_dim 64 only.  bf16 products, fp32 accumulation, probabilities rounded to bf16 before P V (the arithmetic of the
+ * single-query forms of svla_attn_fwd_bf16); klen[r] <= 0: a zero row and -inf LSE.  The cost follows klen[r], not kv_rows (csrc/attn_decode_rows.hip).
+ * SVLA_EINVAL, nothing launched: rows or H <= 0, head_dim != 64, kv_rows outside 1..1024, ld, ldq or ldo not a multiple of 8, klen NULL. */
+int svla_attn_decode_rows_bf16(const svla_bf16* Q, long ldq, const svla_bf16* K, const svla_bf16* V, long ld, svla_bf16* O, long ldo, float* LSE, const int* klen,
+                               const int* cache_row, int rows, int H, int head_dim, float scale, int kv_rows, void* stream);
 /* llama FeedForward gate silu(a)*b (llama/model.py:359-360) on [a | b] rows. */
 int svla_swiglu_fwd(const svla_bf16* ab, long M, int Hd, svla_bf16* g, void* stream);
 int svla_swiglu_bwd(const svla_bf16* ab, const svla_bf16* dg, long M, int Hd, svla_bf16* dab, void* stream);

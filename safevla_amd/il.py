@@ -207,6 +207,14 @@ class EarlyFusionCnnTransformer(Tower):
                                               sampling, **kw)
 
     @classmethod
+    def build_vector_agent(cls, model_version="small_3", input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"), loss="action", device="cuda",
+                           sampling="greedy", num_episodes: int = 1, max_seq_len: int = 1000, tokenizer=None, generator: Optional[torch.Generator] = None,
+                           ckpt_pth: Optional[str] = None):
+        """The model of ``build_model`` behind ``EarlyFusionCnnTransformerVectorAgent``: ``num_episodes`` evaluation episodes served by one set of weights."""
+        return EarlyFusionCnnTransformerVectorAgent(cls.build_model(model_version, input_sensors, loss, device=device, ckpt_pth=ckpt_pth), num_episodes, device,
+                                                    sampling, max_seq_len=max_seq_len, tokenizer=tokenizer, generator=generator)
+
+    @classmethod
     def version_config(cls, model_version):
         """(fusion layers, decoder layers, image-feature width, text encoder, transformer width, fusion heads, decoder heads) of a preset"""
         v = cls.VERSIONS[model_version]
@@ -271,6 +279,12 @@ class EarlyFusionCnnTransformerAgent:
 
     def __init__(self, model: EarlyFusionCnnTransformer, device="cuda", sampling: str = "greedy", max_seq_len: int = 1000, tokenizer=None,
                  generator: Optional[torch.Generator] = None):
+        self._setup(model, device, sampling, max_seq_len, tokenizer, generator)
+        self._warned_window = False
+        self.reset()
+
+    def _setup(self, model, device, sampling, max_seq_len, tokenizer, generator):
+        """What the single and the vector agent share: the checks of the constructor, the KV-cache window, the action list, the tokenizer, eval mode"""
         from .agent import ALL_STRETCH_ACTIONS
         if sampling not in ("greedy", "sample"):
             raise NotImplementedError(f"sampling {sampling!r}: 'greedy' (argmax) or 'sample' (categorical), utils/nn_utils.py sample_action_index_from_logits")
@@ -280,7 +294,6 @@ class EarlyFusionCnnTransformerAgent:
             raise NotImplementedError(f"the online agent needs 64-wide decoder heads; this preset has heads of {model.hdim_dec} "
                                       "(TransformerConfig(n, 768, 8): base_6, siglip_base_3_6) -- use forward(batch) on whole windows")
         self.model, self.device, self.sampling, self.max_seq_len = model, torch.device(device), sampling, min(max_seq_len, 1024, model.max_steps)
-        self._warned_window = False
         self.action_list = list(ALL_STRETCH_ACTIONS)
         self.generator = generator
         if tokenizer is None and model.text_encoder_name == "t5-small":
@@ -288,7 +301,6 @@ class EarlyFusionCnnTransformerAgent:
             tokenizer = GoalTokenizer()
         self.tokenizer = tokenizer
         self.model.eval()
-        self.reset()
 
     def reset(self):
         self.curr_t = 0
@@ -349,3 +361,134 @@ class EarlyFusionCnnTransformerAgent:
             self.cache["last_actions"] = idx
         self.curr_t += 1
         return self.action_list[idx], probs
+
+
+def ring_slot(age: int, window: int):
+    """Step ``age`` of an episode on a KV ring of ``window`` slots -> (slot the step is written to, number of slots its query reads).  The llama decoder applies
+    no RoPE and the time encoding is added to the input, so a single query does not care in which order its keys lie: slots [0, klen) ARE the last
+    min(age + 1, window) steps.  The same slot holds the step's decoder input in the history ring that the sliding window of
+    early_fusion_tsfm_models.py:491-497 is decoded from once the episode is older than the window."""
+    return age % window, min(age + 1, window)
+
+
+class EarlyFusionCnnTransformerVectorAgent:
+    """``num_episodes`` online episodes of the imitation-learning model behind one set of weights: what ``EarlyFusionCnnTransformerAgent`` does for one episode
+    (early_fusion_tsfm_models.py:366-520), for a vector of them that start, end and stall independently -- the evaluation workers of the reference hold one model
+    copy each.  ``reset(slot, goal_spec)`` starts an episode in a slot; ``get_actions({slot: observations})`` steps any non-empty subset of the started slots as ONE
+    compact batch and returns ``{slot: (action_str, action_probs)}``; slots that are absent keep their cache and their age.
+
+    Every slot owns one row of the llama KV caches and one row of a history of decoder inputs, both rings of W = min(max_seq_len, 1024, model.max_steps) slots
+    (``ring_slot``).  Up to W steps an episode takes the KV-cached step: every step attends to the whole episode.  An episode longer than W attends to its last W
+    steps, as the reference's agent does (:491-497), without a warning or a restart: from step W on it is decoded anew over the window held in the history ring
+    (``Tower._decoder_window_fwd``), because the cached K / V of the decoder layers above the first carry the steps in front of the window in their context -- only
+    the first layer's are functions of their own step.  Such a step costs a W-step decoder pass per episode instead of one token's.  Goals of
+    different lengths (t5 presets) are right-padded to the longest; the padding is masked in the text encoder and hidden from every fusion layer, so an episode's
+    actions do not depend on which other episodes share its batch.  The frozen text encoder reruns only when a ``reset`` brought a new goal.
+
+    The slots' cache rows are the model's: a single agent on the same model writes cache row 0, so run one kind of agent on a model at a time."""
+
+    _setup, _goal = EarlyFusionCnnTransformerAgent._setup, EarlyFusionCnnTransformerAgent._goal
+
+    def __init__(self, model: EarlyFusionCnnTransformer, num_episodes: int, device="cuda", sampling: str = "greedy", max_seq_len: int = 1000, tokenizer=None,
+                 generator: Optional[torch.Generator] = None):
+        if not 1 <= int(num_episodes) <= 1024:
+            raise ValueError(f"num_episodes = {num_episodes}: 1 ... 1024 episodes per vector agent")
+        self._setup(model, device, sampling, max_seq_len, tokenizer, generator)
+        self.num_episodes = int(num_episodes)
+        self._age = [None] * self.num_episodes                 # host-side: steps taken in the slot's episode (None: not started)
+        self._last = [START_TOKEN] * self.num_episodes
+        self._goal_ids = [None] * self.num_episodes            # token ids without padding, as tuples
+        self._goals = None                                     # _goal_table() of the current goals; None: a goal changed
+
+    def get_action_list(self):
+        return self.action_list
+
+    def age(self, slot: int) -> int:
+        return self._age[self._started(slot)]
+
+    def _slot(self, slot) -> int:
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.num_episodes:
+            raise KeyError(slot)
+        return int(slot)
+
+    def _started(self, slot) -> int:
+        slot = self._slot(slot)
+        if self._age[slot] is None:
+            raise KeyError(slot)
+        return slot
+
+    def reset(self, slot: int, goal_spec):
+        slot = self._slot(slot)
+        g = self._goal(goal_spec)
+        if isinstance(g, dict):
+            ids = g["input_ids"].reshape(-1)
+            if "attention_mask" in g:                          # right-padded ids: keep the tokens
+                ids = ids[: int(g["attention_mask"].sum())]
+        else:
+            ids = g.reshape(-1)
+        ids = tuple(int(v) for v in ids.tolist())
+        if ids != self._goal_ids[slot]:
+            self._goal_ids[slot], self._goals = ids, None
+        self._age[slot], self._last[slot] = 0, START_TOKEN
+
+    def _goal_table(self):
+        """-> (ids_key, all slots' goals as the ``goals`` of ``prepare`` (row = slot, right-padded to the longest, length L; a slot that never started holds one
+        end-of-sequence token), fusion key mask [N, S] uint8 or None without padding, goal length per slot, L); rebuilt when a goal changed"""
+        if self._goals is None:
+            m, dev = self.model, self.device
+            rows = [g if g is not None else (1,) for g in self._goal_ids]
+            lens = [len(g) for g in rows]
+            L = max(lens)
+            ids = torch.tensor([list(g) + [0] * (L - len(g)) for g in rows], dtype=torch.int64)
+            if m.text_encoder_name == "t5-small":
+                mask = (torch.arange(L)[None, :] < torch.tensor(lens)[:, None])
+                goals = dict(input_ids=ids.to(dev), attention_mask=mask.to(torch.int64).to(dev))
+                kvalid = torch.cat([torch.ones(len(rows), m.text_off, dtype=torch.uint8), mask.to(torch.uint8)], 1).contiguous().to(dev) if min(lens) < L else None
+            else:                                              # SigLIP: a fixed context, nothing to hide (slots that never started: pad ids up to it)
+                goals, kvalid, lens = ids.to(dev), None, [L] * len(rows)
+            self._goals = (("vector", tuple(rows)), goals, kvalid, lens, L)
+        return self._goals
+
+    @torch.no_grad()
+    def get_actions(self, observations: Dict[int, Dict]) -> Dict[int, tuple]:
+        m, dev = self.model, self.device
+        if not observations:
+            raise ValueError("get_actions needs the observations of at least one started slot")
+        n, W = len(observations), self.max_seq_len
+        # episodes that have outlived their window go last: the model decodes them over the window instead of against the KV ring (stable: the order stays otherwise)
+        order = sorted(((self._started(s), o) for s, o in observations.items()), key=lambda so: self._age[so[0]] >= W)
+        slots, obs = [s for s, _ in order], [o for _, o in order]
+        key, goals, kvalid, lens, L = self._goal_table()
+        ring = [ring_slot(self._age[s], W) for s in slots]
+        # the step's one small upload: cache row (= slot), ring slot to write, slots to read, per row
+        rows = torch.tensor([slots, [p for p, _ in ring], [k for _, k in ring]], dtype=torch.int32).to(dev)
+        col = lambda v, dt: torch.as_tensor(np.asarray(v)).to(dt).reshape(n, 1)
+        batch = {"goals": goals, "time_ids": col([self._age[s] for s in slots], torch.int64)}      # the episode's age, as early_fusion_tsfm_models.py:480
+        if m.has_prev:
+            batch["last_actions"] = col([self._last[s] for s in slots], torch.int64)
+        if m.has_hand:
+            batch["an_object_is_in_hand"] = col([np.asarray(o.get("an_object_is_in_hand", 0)).reshape(-1)[0] for o in obs], torch.int64)
+        for cam in m.cameras:
+            if torch.is_tensor(obs[0][cam]):
+                x = torch.stack([o[cam] for o in obs])
+            else:
+                x = torch.as_tensor(np.stack([np.asarray(o[cam]) for o in obs]))
+            batch[cam] = x.reshape((n, 1) + tuple(x.shape[1:]))
+        prep = m.prepare(batch)
+        prep.acting = True
+        prep.ids_key = key                                     # eval mode: the frozen text encoder reruns only when a goal changed
+        prep.gid = rows[0]                                     # row -> its slot's goal
+        prep.row_cache, prep.row_pos, prep.row_klen = rows[0], rows[1], rows[2]
+        prep.row_window, prep.row_slide = W, sum(self._age[s] >= W for s in slots)
+        if kvalid is not None and any(lens[s] < L for s in slots):
+            prep.fusion_kvalid = kvalid.index_select(0, rows[0])
+        m._ensure_caches(self.num_episodes)
+        m._ensure_history(self.num_episodes, W)
+        logits, _, _ = m.run_forward(prep, need_grad=False)
+        probs = torch.softmax(logits.reshape(n, -1).float(), -1)
+        idx = torch.argmax(probs, -1) if self.sampling == "greedy" else torch.multinomial(probs, 1, generator=self.generator).reshape(-1)
+        out = {}
+        for j, (s, i) in enumerate(zip(slots, idx.tolist())):  # the call's one host read
+            self._last[s], self._age[s] = i, self._age[s] + 1
+            out[s] = (self.action_list[i], probs[j])
+        return out

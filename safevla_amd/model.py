@@ -213,7 +213,7 @@ class Tower(nn.Module):
         # acting path: llama KV caches (+ version: recorded steps hold pointers into them), eval-mode text-feature cache, gamma-folded decoder weights (refresh_folded), norm-fused
         # GEMMs in the acting step's decoder / the frozen text encoder (None: by size).  Below: step counter, dropout seed, step indices of recorded / captured passes (device memory)
         self._kv, self._kv_version, self._t5_cache, self._wg, self._wg_dirty, self.rms_fused, self.t5_fused = None, 0, (None, None), {}, True, True, None
-        self._t_dev = self._seed_dev = self._seed_dev_buf = self._ar_steps = self._last_full_logits = None
+        self._t_dev = self._seed_dev = self._seed_dev_buf = self._ar_steps = self._last_full_logits = self._hist = None
         dec = arena.declare
         ve = self.visual_encoder = _NS()
         dec(ve, "fusion_token", (D,), "tok")
@@ -369,6 +369,11 @@ class Tower(nn.Module):
             self._kv_version += 1        # recorded steps hold pointers into the caches: new caches, new plans
             self._kv = [torch.zeros(B, self.max_steps, 2 * self.D, device=self.device_, dtype=self.adt) for _ in self.decoder.layers]
 
+    def _ensure_history(self, n: int, window: int):
+        """decoder inputs of the last ``window`` steps of ``n`` episodes (vector steps with ``Prep.row_window``: ``_decoder_rows_fwd``)"""
+        if self._hist is None or self._hist.shape[0] < n or self._hist.shape[1] != window:
+            self._hist = torch.zeros(n, window, self.D, device=self.device_, dtype=self.adt)
+
     def cache_select(self, keep: list):
         if self._kv is not None:
             idx = torch.as_tensor(keep, device=self.device_, dtype=torch.long)
@@ -403,7 +408,12 @@ class Tower(nn.Module):
     def run_forward(self, prep: "Prep", need_grad: bool):
         """-> logits [T, B, A], values [T, B, 1], the saved activations for ``run_backward`` (opaque to callers; None without ``need_grad``)"""
         D, T, B, S = self.D, prep.T, prep.B, prep.S
-        if T > 1 or need_grad or not prep.acting or self.time_step_counter >= self.max_steps:
+        per_row = prep.row_pos is not None
+        if per_row and (T > 1 or need_grad or not prep.acting or prep.row_klen is None):
+            raise ValueError("row_pos / row_klen: the acting step on per-row KV rings is a T = 1 forward without gradients, with both fields given")
+        if prep.fusion_kvalid is not None and (need_grad or self.fp8_attention):
+            raise ValueError("fusion_kvalid: the key-padding mask of the fusion encoder exists in the bf16 / fp32 forward only (no backward, no fp8 form)")
+        if not per_row and (T > 1 or need_grad or not prep.acting or self.time_step_counter >= self.max_steps):
             self.time_step_counter = 0
         seed, site = self._drop_sites()
         c = dict(drop_seed=seed, fusion=[])  # saved activations
@@ -424,7 +434,7 @@ class Tower(nn.Module):
             # acting: one new token per env against the KV cache.  A one-step UPDATE batch (need_grad) takes the sequence form -- a sequence of length one has no
             # history to attend to, and the backward needs the saved activations -- and so does a batch whose Prep says ``acting = False`` (the imitation-learning
             # model's ``forward(batch)`` on one-step windows: independent sequences, never the cache of an earlier call; its online agent sets ``acting = True``)
-            xd, c["dec"] = self._decoder_step_fwd(xd, prep), []
+            xd, c["dec"] = (self._decoder_rows_fwd(xd, prep) if per_row else self._decoder_step_fwd(xd, prep)), []
         else:
             xd, c["dec"] = self._decoder_seq_fwd(xd, prep, need_grad)
         logits, values = self._heads_fwd(xd, prep, c, need_grad)
@@ -484,7 +494,8 @@ class Tower(nn.Module):
                 att = dict(absorbed=True, eq=eq, qt=qt, cc=cc, sig=sig, prob=prob)
             else:
                 kv = ops.gemm_nt(xf, w[f"f{i}.in"][D:], M, 2 * D, D, bias=b_in[D:])
-                ao, lse = ops.attn_fwd(q0, kv, kv[:, D:], 2 * D, R, S, H, SCF, save_lse=need_grad, Sq=1, ldq=D, drop=site(i, 0), head_dim=self.hdim)
+                ao, lse = ops.attn_fwd(q0, kv, kv[:, D:], 2 * D, R, S, H, SCF, kvalid=prep.fusion_kvalid, save_lse=need_grad, Sq=1, ldq=D, drop=site(i, 0),
+                                       head_dim=self.hdim)
                 att = dict(absorbed=False, kv=kv, lse=lse)
             xo, post = self._fusion_post_fwd(i, ao, R, xf, S * D, S, False, site, need_grad)
             return xo, (dict(pruned=True, x=xf, q0=q0, ao=ao, **att, **post) if need_grad else None)
@@ -495,7 +506,8 @@ class Tower(nn.Module):
             ao, lse = ops.attn_fp8_fwd(f8, SCF, save_lse=need_grad, drop=site(i, 0))
             qkv = None                       # the backward reads the e4m3 copies
         else:
-            ao, lse = ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, R, S, H, SCF, save_lse=need_grad, drop=site(i, 0), head_dim=self.hdim)
+            ao, lse = ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, R, S, H, SCF, kvalid=prep.fusion_kvalid, save_lse=need_grad, drop=site(i, 0),
+                                   head_dim=self.hdim)
         xo, post = self._fusion_post_fwd(i, ao, M, xf, None, 1, need_grad and self.adt == BF16, site, need_grad)
         return xo, (dict(pruned=False, x=xf, qkv=qkv, f8=f8, ao=ao, lse=lse, **post) if need_grad else None)
 
@@ -512,13 +524,21 @@ class Tower(nn.Module):
         return xo, dict(h1=h1, x1=x1, n1=(m1, r1), f1=f1, f1b=f1b, h2=h2, n2=(m2, r2))
 
     def _decoder_step_fwd(self, xd, prep):
-        """The llama decoder as one KV-cached step: env b attends to cache slots >= max(counter - time_step_b, 0), its current episode (allenact_dino_transformer.py:388-397)"""
-        D, HD, B, w, SCD = self.D, self.dec_hidden, prep.B, self._w, self.hdim_dec ** -0.5
+        """The llama decoder as one KV-cached step: env b attends to cache slots >= max(counter - time_step_b, 0), its current episode (allenact_dino_transformer.py:388-397).
+        With ``prep.row_pos`` / ``row_klen`` (/ ``row_cache``): every row on a KV ring of its own instead (ops.kv_append_rows, ops.attn_decode_rows)."""
+        D, HD, B, w, SCD = self.D, self.dec_hidden, xd.shape[0], self._w, self.hdim_dec ** -0.5      # B: prep.B, or the leading rows of a vector step
         if self.hdim_dec != 64:
             raise NotImplementedError("KV-cached single steps need 64-wide decoder heads (MFMA / decode attention kernels)")
         t, t_dev = self.time_step_counter, self._t_dev
-        self._ensure_caches(B)
-        if t_dev is None:
+        per_row = prep.row_pos is not None
+        if not per_row:
+            self._ensure_caches(B)
+        if per_row:
+            # per-row KV rings (a vector of episodes with ages of their own): slot, length and cache row of every row come from device memory; the caller has
+            # allocated the caches (``_ensure_caches(row_cache.max() + 1)``), and the step counter is neither read nor advanced
+            if self._kv is None:
+                raise ValueError("row_pos: allocate the KV caches with _ensure_caches(n) before the first per-row step")
+        elif t_dev is None:
             start = torch.clamp(t - prep.time_step, min=0)
             kvalid = (torch.arange(t + 1, device=self.device_)[None, :] >= start[:, None]).to(torch.uint8).contiguous()
             S_att = t + 1
@@ -545,30 +565,75 @@ class Tower(nn.Module):
         for i, l in enumerate(self.decoder.layers):
             qkv = normed_gemm(xd, l.attention_norm, f"d{i}.qkv", 3 * D)
             cache = self._kv[i]
-            if t_dev is None:
-                cache[:B, t].copy_(qkv[:, D:])
-            elif self.adt == BF16:
-                ops.kv_append(qkv[:, D:], 3 * D, cache, t_dev, B, 2 * D)
-            else:
-                cache[:B].index_copy_(1, t_dev.view(1), qkv[:, D:].unsqueeze(1))
             cv = cache.view(-1, 2 * D)
-            ao, _ = ops.attn_fwd(qkv, cv, cv[:, D:], 2 * D, B, S_att, self.Hdec, SCD, kvalid=kvalid, save_lse=False, Sq=1, ldq=3 * D,
-                                 kv_rows=self.max_steps)
+            if per_row:
+                ops.kv_append_rows(qkv[:, D:], 3 * D, cache, prep.row_cache, prep.row_pos, B, 2 * D)
+                ao, _ = ops.attn_decode_rows(qkv, 3 * D, cv, cv[:, D:], 2 * D, prep.row_klen, prep.row_cache, B, self.Hdec, SCD, self.max_steps)
+            else:
+                if t_dev is None:
+                    cache[:B, t].copy_(qkv[:, D:])
+                elif self.adt == BF16:
+                    ops.kv_append(qkv[:, D:], 3 * D, cache, t_dev, B, 2 * D)
+                else:
+                    cache[:B].index_copy_(1, t_dev.view(1), qkv[:, D:].unsqueeze(1))
+                ao, _ = ops.attn_fwd(qkv, cv, cv[:, D:], 2 * D, B, S_att, self.Hdec, SCD, kvalid=kvalid, save_lse=False, Sq=1, ldq=3 * D,
+                                     kv_rows=self.max_steps)
             h = ops.gemm_nt(ao, w[f"d{i}.wo"], B, D, D, residual=xd)
             gg = ops.swiglu_fwd(normed_gemm(h, l.ffn_norm, f"d{i}.w13", 2 * HD), B, HD)
             xd = ops.gemm_nt(gg, w[f"d{i}.w2"], B, D, HD, residual=h)
-        self.time_step_counter += 1
+        if not per_row:
+            self.time_step_counter += 1
         return xd
 
-    def _decoder_seq_fwd(self, xd, prep, need_grad):
-        """The llama decoder over whole sequences, rows (b*T + t), causal within a trajectory -> (output rows, saved activations per layer)"""
+    def _decoder_rows_fwd(self, xd, prep):
+        """The acting step of a vector of episodes (``prep.row_pos`` ...): the first B - row_slide rows take the KV-cached step on their rings; the trailing
+        ``row_slide`` rows are episodes older than their window of ``row_window`` steps and are decoded over that window (``_decoder_window_fwd``).  With a window
+        given, every row's decoder input goes into its history ring first (slot row_pos of history row row_cache; ``_ensure_history``)."""
+        B, D, ns = prep.B, self.D, int(prep.row_slide or 0)
+        if self.hdim_dec != 64:
+            raise NotImplementedError("KV-cached single steps need 64-wide decoder heads (MFMA / decode attention kernels)")
+        if self.adt != BF16:
+            raise NotImplementedError("the acting step on per-row KV rings exists on the bf16 product path only")
+        if prep.row_window:
+            if self._hist is None or prep.row_cache is None:
+                raise ValueError("row_window: allocate the history with _ensure_history(n, window) and give row_cache")
+            ops.kv_append_rows(xd, D, self._hist, prep.row_cache, prep.row_pos, B, D)
+        elif ns:
+            raise ValueError("row_slide needs row_window")
+        outs = ([self._decoder_step_fwd(xd[:B - ns], prep)] if ns < B else []) + ([self._decoder_window_fwd(prep, B - ns, ns)] if ns else [])
+        return outs[0] if len(outs) == 1 else torch.cat(outs)
+
+    def _decoder_window_fwd(self, prep, first, n):
+        """Rows first ... first + n of a vector step whose episodes have outlived their window W = ``prep.row_window``: the reference's agent decodes the last W
+        embedded steps anew (early_fusion_tsfm_models.py:491-497: decoder_input[:, -max_seq_len:]) -- cached K / V of the layers above the first would carry steps
+        older than the window in their context.  The window is read from the history ring, oldest step first, and runs through the sequence form of the decoder;
+        its causal attention is ops.attn_decode_rows with one query row per (episode, position): position t reads the t + 1 first keys of its episode, for any
+        W <= 1024 (the tile kernels of the sequence form end at 512 keys).  -> the rows of the newest position [n, D]"""
+        W, D, dev = int(prep.row_window), self.D, self.device_
+        ar = torch.arange(W, device=dev)
+        slot = (prep.row_pos[first:first + n].long()[:, None] + 1 + ar[None, :]) % W                      # oldest ... newest (= row_pos, just written)
+        xw = self._hist[prep.row_cache[first:first + n].long()[:, None], slot].reshape(n * W, D)      # rows (b * W + t)
+        crow = torch.arange(n, device=dev, dtype=torch.int32).repeat_interleave(W)
+        klen = (ar + 1).to(torch.int32).repeat(n)
+        pw = Prep()
+        pw.T, pw.B, pw.R = W, n, n * W
+        attn = lambda qkv: ops.attn_decode_rows(qkv, 3 * D, qkv[:, D:], qkv[:, 2 * D:], 3 * D, klen, crow, n * W, self.Hdec, self.hdim_dec ** -0.5, W)
+        xo, _ = self._decoder_seq_fwd(xw, pw, False, attn=attn)
+        return xo.view(n, W, D)[:, W - 1].contiguous()
+
+    def _decoder_seq_fwd(self, xd, prep, need_grad, attn=None):
+        """The llama decoder over whole sequences, rows (b*T + t), causal within a trajectory -> (output rows, saved activations per layer).
+        ``attn``: the causal attention as a callable qkv -> (ao, lse) instead of the block-causal tile kernels (forward only: ``_decoder_window_fwd``)"""
         D, HD, T, B, R, w, SCD = self.D, self.dec_hidden, prep.T, prep.B, prep.R, self._w, self.hdim_dec ** -0.5
         dl = []
         for i, l in enumerate(self.decoder.layers):
             n1, _, r1 = ops.norm_fwd(xd, l.attention_norm.weight, None, 1e-5, R, rms=True, save_stats=need_grad, D=D)
             qkv = ops.gemm_nt(n1, w[f"d{i}.qkv"], R, 3 * D, D)
-            ao, lse = ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, B, T, self.Hdec, SCD, head_dim=self.hdim_dec, mask_mode=ops.MASK_BLOCK_CAUSAL,
-                                   traj=prep.traj_bt, save_lse=need_grad)
+            if attn is not None:
+                ao, lse = attn(qkv)
+            else:
+                ao, lse = ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, B, T, self.Hdec, SCD, head_dim=self.hdim_dec, mask_mode=ops.MASK_BLOCK_CAUSAL,
+                                       traj=prep.traj_bt, save_lse=need_grad)
             h = ops.gemm_nt(ao, w[f"d{i}.wo"], R, D, D, residual=xd)
             n2, _, r2 = ops.norm_fwd(h, l.ffn_norm.weight, None, 1e-5, R, rms=True, save_stats=need_grad, D=D)
             ab = ops.gemm_nt(n2, w[f"d{i}.w13"], R, 2 * HD, D)
@@ -917,12 +982,18 @@ class Prep:
     """Per-forward inputs shared by the three towers (built once).  Producers fill the fields one by one; a name that is not declared here is an AttributeError.
     R = T * B rows of S = 1 + ncam * 84 + L fusion tokens; U unique goals of L tokens; tokens [R, ncam, 84, dino_dim]; prev_actions, masks, hand, time_step [R]
     (hand: None without the in-hand sensor; prev_actions, masks: None without the previous-action sensor); traj_bt [B, T]; ids, attn_mask [U, L]; gid [R]: row -> goal.
-    Optional: ``acting`` (a T = 1 pass under no_grad is a step against the KV caches), ``ids_key`` (host-side identity of the goals: eval-mode text-feature cache), ``attn_mask_u8`` (attn_mask in the kernels' format), ``kvalid_static`` (recorded steps: the KV-window mask [B, max_steps])."""
+    Optional: ``acting`` (a T = 1 pass under no_grad is a step against the KV caches), ``ids_key`` (host-side identity of the goals: eval-mode text-feature cache), ``attn_mask_u8`` (attn_mask in the kernels' format), ``kvalid_static`` (recorded steps: the KV-window mask [B, max_steps]).
+    ``fusion_kvalid`` (uint8 [R, S]: the fusion tokens of a row that are keys -- hides the padded goal tokens of a batch of goals of different lengths; forward only).
+    ``row_pos``, ``row_klen`` (int32 [B], given together) and ``row_cache`` (int32 [B] or None = identity): the acting step on per-row KV rings -- row b writes slot
+    row_pos[b] of cache row row_cache[b] and attends to that cache row's first row_klen[b] slots; the tower's own step counter takes no part.  ``row_window`` (int W)
+    and ``row_slide`` (int): with a window every row's decoder input is kept in a history ring of W slots, and the trailing row_slide rows -- episodes that have
+    outlived W steps -- are decoded anew over their last W steps instead of against the KV ring."""
     __slots__ = ("T", "B", "R", "S", "L", "U", "tokens", "prev_actions", "masks", "hand", "time_step", "traj_bt", "ids", "attn_mask", "gid",
-                 "acting", "ids_key", "attn_mask_u8", "kvalid_static")
+                 "acting", "ids_key", "attn_mask_u8", "kvalid_static", "fusion_kvalid", "row_cache", "row_pos", "row_klen", "row_window", "row_slide")
 
     def __init__(self):
         self.acting, self.ids_key, self.attn_mask_u8, self.kvalid_static = True, None, None, None
+        self.fusion_kvalid = self.row_cache = self.row_pos = self.row_klen = self.row_window = self.row_slide = None
 
 
 class _ActingState(Prep):

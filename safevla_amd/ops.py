@@ -678,6 +678,34 @@ def kv_append(src, ld_src, cache, t_dev, B, width):
     lib().call("svla_kv_append_bf16", _p(src), int(ld_src), _p(cache), int(cache.shape[1]), int(width), _p(t_dev), int(B), _stream())
 
 
+def kv_append_rows(src, ld_src, cache, cache_row, pos, rows, width):
+    """cache[cache_row[r], pos[r], :width] = src[r, :width] for r < rows (cache: [cache rows, slots, width] bf16; cache_row: int32 [rows] device tensor or None =
+    identity; pos: int32 [rows] device tensor, a negative entry skips its row).  Slot and cache row are read on the device: the arguments are step-independent."""
+    _chk(cache, BF16, "cache")
+    _chk(pos, torch.int32, "pos")
+    if cache_row is not None:
+        _chk(cache_row, torch.int32, "cache_row")
+    lib().call("svla_kv_append_rows_bf16", _p(src), int(ld_src), _p(cache), int(cache.shape[1]), int(width), _p(cache_row), _p(pos), int(rows), _stream())
+
+
+def attn_decode_rows(q, ldq, k, v, ld, klen, cache_row, rows, H, scale, kv_rows, out=None, ldo=None, save_lse=False, head_dim=64):
+    """One query per row against that row's own KV ring (csrc/attn_decode_rows.hip): row r reads keys [0, min(klen[r], kv_rows)) of cache row cache_row[r] (None: r),
+    ``kv_rows`` (<= 1024) token rows per cache row.  klen, cache_row: int32 [rows] device tensors.  -> (out [rows, H * 64] bf16, lse [rows, H] fp32 or None); a row
+    with klen <= 0 comes out as zeros.  64-wide heads, bf16 only; anything else raises ``SvlaError`` (invalid argument) and launches nothing."""
+    _chk(q, BF16, "q")
+    _chk(klen, torch.int32, "klen")
+    if cache_row is not None:
+        _chk(cache_row, torch.int32, "cache_row")
+    W = H * head_dim
+    if out is None:
+        out = torch.empty(rows, W, device=q.device, dtype=BF16)
+    ldo = ldo if ldo is not None else out.stride(-2)
+    lse = torch.empty(rows, H, device=q.device, dtype=F32) if save_lse else None
+    lib().call("svla_attn_decode_rows_bf16", _p(q), int(ldq), _p(k), _p(v), int(ld), _p(out), int(ldo), _p(lse), _p(klen), _p(cache_row), int(rows), int(H), int(head_dim),
+               float(scale), int(kv_rows), _stream())
+    return out, lse
+
+
 def swiglu_fwd(ab, M, Hd, out=None):
     if out is None:
         out = torch.empty(M, Hd, device=ab.device, dtype=ab.dtype)
