@@ -164,7 +164,8 @@ int svla_colsum_f32(const float* X, long ldx, int M, int N, int row_stride, floa
  * head_dim 64, forward, 512 < S <= 1024: the single-query ("decode") form only -- Sq == 1, no bias, mask_mode 0, no dropout; kvalid [rows,S] or null, kv_rows >= S,
  * ldq, optional LSE [rows,H] (natural log) -- on csrc/attn_decode_long.hip: the KV-cached acting step of the llama decoder over a cache window of up to 1024 slots
  * (the reference's policies and llama caches are built for 1000 steps, its online evaluation runs episodes of 600 and 1000).  Only valid keys are read; a row without
- * a valid key yields zeros; the cost follows the number of 32-key blocks that hold a valid key, not S.  Every other form above 512 keys, and S > 1024, is SVLA_EINVAL.
+ * a valid key yields zeros; the cost follows the number of 32-key blocks that hold a valid key, not S.  Every other form above 512 keys, and S > 1024, is SVLA_EINVAL
+ * HERE; the causal sequence forward of a whole episode (all S queries, up to 1024 keys) is an entry of its own, svla_attn_causal_fwd_bf16 at the end of this header.
  * mask_mode 0: none (nn.MultiheadAttention in the fusion encoder, allenact_dino_transformer.py:545-552,702-708);
  * 1: block-causal on traj ids (allenact_dino_transformer.py:398-402 + llama/model.py:317-319).
  * bias [H,S,S] + kvalid [rows,S]: T5 self-attention.  LSE [rows,H,Sq] is saved for the backward.
@@ -505,6 +506,19 @@ int svla_swiglu_fwd_f32(const float* ab, long M, int Hd, float* g, void* stream)
 int svla_swiglu_bwd_f32(const float* ab, const float* dg, long M, int Hd, float* dab, void* stream);
 int svla_embed_gather_f32(const float* table, const int64_t* ids, long n, int D, float* out, void* stream);
 int svla_dropout_f32(float* x, long rows, int N, const svla_dropout* drop, void* stream);
+
+/* ---- causal attention over whole episodes ----------------------------------------------------------------------------------------
+ * (Declared last: svla_replay_calls numbers the entry points in declaration order, and a new one must not move the others.)
+ * The sequence form of the llama decoder's attention (llama/model.py:249-322 with the block-causal traj_index mask of early_fusion_tsfm_models.py:160-178, 491-497)
+ * for up to 1024 keys, forward only, bf16, head_dim 64 (csrc/attn_seq_long.hip): O[i] = softmax_j(scale * q_i.k_j) V over the keys j <= i with
+ * traj[r,i] == traj[r,j]; traj == NULL: plain causal.  A query always sees itself.  Token t of batch row r at (r*S + t) * ld for Q, K and V alike (the fused qkv
+ * rows of the decoder), O rows ldo apart, LSE [rows,H,S] (natural log, the layout svla_attn_bwd_bf16 reads) or NULL, traj [rows,S] int32 or NULL.  The arithmetic of
+ * svla_attn_fwd_bf16 with mask_mode 1 (bf16 products, fp32 scores and accumulation, probabilities rounded to bf16 before P V, the denominator summed from the
+ * unrounded values) with an online softmax over 64-key tiles streamed through LDS, so the two agree to rounding, not bit for bit.  1 <= S <= 1024; the model
+ * routes only S > 512 here.  SVLA_EINVAL, nothing launched: head_dim != 64, rows or H <= 0, S outside 1..1024, ld or ldo not a multiple of 8 or below H*64, a NULL
+ * Q, K, V or O.  No dropout, bias, kvalid, Sq or kv_rows; no backward above 512 keys (svla_attn_bwd_bf16). */
+int svla_attn_causal_fwd_bf16(const svla_bf16* Q, const svla_bf16* K, const svla_bf16* V, long ld, svla_bf16* O, long ldo, float* LSE, int rows, int S, int H,
+                              int head_dim, float scale, const int* traj, void* stream);
 
 #ifdef __cplusplus
 }

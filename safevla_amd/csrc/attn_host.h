@@ -40,6 +40,7 @@ struct AttnLimits {
 //                                                   S              bias   masks  ldo ldd lddq
 constexpr AttnLimits ATTN_FWD_64          = {  1,       512, true,  false, 1, 1, 1};      // attn.hip: tile and decode kernels
 constexpr AttnLimits ATTN_FWD_64_DECODE_L = {513, DECL_MAXS, false, true,  1, 1, 1};      // attn_decode_long.hip; the entry also asks for Sq == 1, no mask, no dropout
+constexpr AttnLimits ATTN_FWD_64_CAUSAL_L = {  1, DECL_MAXS, false, true,  8, 1, 1};      // attn_seq_long.hip: its own entry (svla_attn_causal_fwd_bf16), which also asks for ld, ldo >= H * 64
 constexpr AttnLimits ATTN_FWD_96          = {  1,       256, false, true,  4, 1, 1};      // attn_hd96.hip
 constexpr AttnLimits ATTN_BWD_64          = {  1,       256, true,  false, 1, 1, 8};      // attn.hip
 constexpr AttnLimits ATTN_BWD_64_LONG     = {257,       512, false, true,  8, 4, 4};      // attn_long.hip

@@ -188,6 +188,8 @@ class EarlyFusionCnnTransformer(Tower):
 
     # ---- reference forward API --------------------------------------------------------------------------------------------------
     def forward(self, batch: Dict) -> Dict[str, torch.Tensor]:
+        # whole episodes (512 < T <= 1000 steps) run forward only -- under torch.no_grad() or in eval mode; what cannot run is refused before the first launch
+        self._check_seq_len(int(batch[self.cameras[0]].shape[1]), torch.is_grad_enabled() and self.training)
         prep = self.prepare(batch, augment=self.data_augmentation)
         logits, _, _ = _TowerFn.apply(self._anchor, self, prep, True, False)      # [T, B, A] fp32
         out = dict(actions_logits=logits.transpose(0, 1))

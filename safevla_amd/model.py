@@ -45,6 +45,10 @@ TEXT_ENCODER_DIMS = {"t5-small": 512, "SigLIPBase": 768, "SigLIPLarge": 1024}
 BF16, F32 = torch.bfloat16, torch.float32
 SEED_STEP = 0x3C6EF35             # what the device-resident dropout seed of a recorded / captured pass advances by per pass (Tower.advance_device_seed, svla_acting_stage)
 _NO_COMPRESSOR_BITS = os.environ.get("SVLA_NO_COMPRESSOR_BITS", "0") == "1"     # A/B switch of the 1-bit compressor ReLU masks
+MAX_TILE_SEQ = 512                # keys of the tile kernels of csrc/attn.hip and of every attention backward: longer sequences are forward only (csrc/attn_seq_long.hip)
+# A/B switch of Tower._decoder_window_fwd (tools/ab_attn_causal_long.py, tests): True keeps windows above MAX_TILE_SEQ steps on one single-query row per (episode,
+# position) instead of the streaming causal kernel.  Read once from SVLA_WINDOW_DECODE_ROWS; a module flag afterwards.
+WINDOW_DECODE_ROWS = os.environ.get("SVLA_WINDOW_DECODE_ROWS", "0") == "1"
 
 
 class _NS(nn.Module):
@@ -408,6 +412,7 @@ class Tower(nn.Module):
     def run_forward(self, prep: "Prep", need_grad: bool):
         """-> logits [T, B, A], values [T, B, 1], the saved activations for ``run_backward`` (opaque to callers; None without ``need_grad``)"""
         D, T, B, S = self.D, prep.T, prep.B, prep.S
+        self._check_seq_len(T, need_grad)
         per_row = prep.row_pos is not None
         if per_row and (T > 1 or need_grad or not prep.acting or prep.row_klen is None):
             raise ValueError("row_pos / row_klen: the acting step on per-row KV rings is a T = 1 forward without gradients, with both fields given")
@@ -607,30 +612,59 @@ class Tower(nn.Module):
         """Rows first ... first + n of a vector step whose episodes have outlived their window W = ``prep.row_window``: the reference's agent decodes the last W
         embedded steps anew (early_fusion_tsfm_models.py:491-497: decoder_input[:, -max_seq_len:]) -- cached K / V of the layers above the first would carry steps
         older than the window in their context.  The window is read from the history ring, oldest step first, and runs through the sequence form of the decoder;
-        its causal attention is ops.attn_decode_rows with one query row per (episode, position): position t reads the t + 1 first keys of its episode, for any
-        W <= 1024 (the tile kernels of the sequence form end at 512 keys).  -> the rows of the newest position [n, D]"""
+        its causal attention is, for W <= 512, ops.attn_decode_rows with one query row per (episode, position): position t reads the t + 1 first keys of its
+        episode.  Above 512 steps (where the tile kernels of the sequence form end) it is the streaming causal kernel of ops.attn_causal_fwd on n rows of W tokens,
+        which reads K and V once per 64-query tile instead of once per query; ``WINDOW_DECODE_ROWS`` keeps the single-query rows there too (A/B, tests).
+        -> the rows of the newest position [n, D]"""
         W, D, dev = int(prep.row_window), self.D, self.device_
         ar = torch.arange(W, device=dev)
         slot = (prep.row_pos[first:first + n].long()[:, None] + 1 + ar[None, :]) % W                      # oldest ... newest (= row_pos, just written)
         xw = self._hist[prep.row_cache[first:first + n].long()[:, None], slot].reshape(n * W, D)      # rows (b * W + t)
-        crow = torch.arange(n, device=dev, dtype=torch.int32).repeat_interleave(W)
-        klen = (ar + 1).to(torch.int32).repeat(n)
         pw = Prep()
         pw.T, pw.B, pw.R = W, n, n * W
-        attn = lambda qkv: ops.attn_decode_rows(qkv, 3 * D, qkv[:, D:], qkv[:, 2 * D:], 3 * D, klen, crow, n * W, self.Hdec, self.hdim_dec ** -0.5, W)
-        xo, _ = self._decoder_seq_fwd(xw, pw, False, attn=attn)
+        if W > MAX_TILE_SEQ and not WINDOW_DECODE_ROWS:
+            pw.traj_bt = None                                                                         # one episode per row: plain causal
+            xo, _ = self._decoder_seq_fwd(xw, pw, False)
+        else:
+            xo, _ = self._decoder_seq_fwd(xw, pw, False, attn=self._window_rows_attn(n, W))
         return xo.view(n, W, D)[:, W - 1].contiguous()
 
+    def _window_rows_attn(self, n, W):
+        """Causal attention over n sequences of W steps as a callable qkv -> (ao, lse) on ops.attn_decode_rows: one single-query row per (sequence, position),
+        position t reading the t + 1 first keys of its sequence (any W <= 1024)"""
+        D, dev = self.D, self.device_
+        crow = torch.arange(n, device=dev, dtype=torch.int32).repeat_interleave(W)
+        klen = (torch.arange(W, device=dev) + 1).to(torch.int32).repeat(n)
+        return lambda qkv: ops.attn_decode_rows(qkv, 3 * D, qkv[:, D:], qkv[:, 2 * D:], 3 * D, klen, crow, n * W, self.Hdec, self.hdim_dec ** -0.5, W)
+
+    def _check_seq_len(self, T, need_grad):
+        """Sequences above MAX_TILE_SEQ steps run forward only, on the bf16 path with 64-wide decoder heads (csrc/attn_seq_long.hip); refused before any launch"""
+        if T <= MAX_TILE_SEQ:
+            return
+        if need_grad:
+            raise ValueError(f"T = {T}: the attention backward ends at {MAX_TILE_SEQ} steps; longer sequences are forward only (torch.no_grad() or eval mode)")
+        if self.adt != BF16:
+            raise ValueError(f"T = {T}: the fp32 verification mode ends at {MAX_TILE_SEQ} steps (the causal forward above that exists in bf16 only)")
+        if self.hdim_dec != 64:
+            raise ValueError(f"T = {T}: decoder heads of {self.hdim_dec} end at {MAX_TILE_SEQ} steps (the causal forward above that is built for 64-wide heads)")
+        if T > MAX_ACTING_WINDOW:
+            raise ValueError(f"T = {T}: the causal forward is limited to {MAX_ACTING_WINDOW} steps")
+
     def _decoder_seq_fwd(self, xd, prep, need_grad, attn=None):
-        """The llama decoder over whole sequences, rows (b*T + t), causal within a trajectory -> (output rows, saved activations per layer).
-        ``attn``: the causal attention as a callable qkv -> (ao, lse) instead of the block-causal tile kernels (forward only: ``_decoder_window_fwd``)"""
+        """The llama decoder over whole sequences, rows (b*T + t), causal within a trajectory -> (output rows, saved activations per layer).  T <= 512: the block-causal
+        tile kernels.  512 < T <= 1024, forward only: the streaming causal kernel (ops.attn_causal_fwd; ``prep.traj_bt`` None: one trajectory per row).
+        ``attn``: the causal attention as a callable qkv -> (ao, lse) instead (forward only: ``_decoder_window_fwd``)"""
         D, HD, T, B, R, w, SCD = self.D, self.dec_hidden, prep.T, prep.B, prep.R, self._w, self.hdim_dec ** -0.5
+        if attn is None:
+            self._check_seq_len(T, need_grad)
         dl = []
         for i, l in enumerate(self.decoder.layers):
             n1, _, r1 = ops.norm_fwd(xd, l.attention_norm.weight, None, 1e-5, R, rms=True, save_stats=need_grad, D=D)
             qkv = ops.gemm_nt(n1, w[f"d{i}.qkv"], R, 3 * D, D)
             if attn is not None:
                 ao, lse = attn(qkv)
+            elif T > MAX_TILE_SEQ:
+                ao, lse = ops.attn_causal_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, B, T, self.Hdec, SCD, traj=prep.traj_bt)
             else:
                 ao, lse = ops.attn_fwd(qkv, qkv[:, D:], qkv[:, 2 * D:], 3 * D, B, T, self.Hdec, SCD, head_dim=self.hdim_dec, mask_mode=ops.MASK_BLOCK_CAUSAL,
                                        traj=prep.traj_bt, save_lse=need_grad)
@@ -1011,6 +1045,8 @@ class _TowerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, tower, prep, want_logits, want_values):
         need = bool(ctx.needs_input_grad[0])   # anchor requires grad <=> grad mode was on at apply() time
+        if prep.T > MAX_TILE_SEQ and not tower.training:
+            need = False                       # a whole episode in eval mode: forward only, nothing saved (backward() then says so); in train mode run_forward refuses
         logits, values, saved = tower.run_forward(prep, need_grad=need)
         ctx.tower, ctx.prep, ctx.saved = tower, prep, saved
         ctx.want = (want_logits, want_values)
@@ -1021,6 +1057,8 @@ class _TowerFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dlogits, dvalues, dfull):
         wl, wv = ctx.want
+        if ctx.saved is None:
+            raise RuntimeError(f"this forward ran without saved activations (T = {ctx.prep.T} > {MAX_TILE_SEQ} steps in eval mode is forward only): no backward")
         ctx.tower.run_backward(ctx.prep, ctx.saved, dlogits.contiguous() if wl else None, dvalues.contiguous() if wv else None,
                                dfull.contiguous() if (wv and ctx.has_full) else None)
         ctx.saved = None
@@ -1398,6 +1436,8 @@ class SafeDinoLLAMATxNavActorCriticSeparate(Tower):
         fast = self._acting_fast(observations, prev_actions, masks)
         if fast is not None:
             return fast, memory
+        for t in self.towers:      # sequences above MAX_TILE_SEQ steps: forward only, refused before the first launch where they cannot run
+            t._check_seq_len(int(prev_actions.shape[0]), torch.is_grad_enabled() and self.training)
         prep = self.prepare(observations, prev_actions, masks)
         if (prep.T == 1 and self._acting_graphs is not None and not torch.is_grad_enabled()
                 and self.time_step_counter < self.max_steps - 1 and all(t.time_step_counter == self.time_step_counter for t in self.towers)):

@@ -706,6 +706,24 @@ def attn_decode_rows(q, ldq, k, v, ld, klen, cache_row, rows, H, scale, kv_rows,
     return out, lse
 
 
+def attn_causal_fwd(q, k, v, ld, rows, S, H, scale, traj=None, save_lse=False, out=None, ldo=None, head_dim=64):
+    """Causal attention of whole episodes, up to 1024 keys (csrc/attn_seq_long.hip): query i of row r sees keys j <= i with ``traj[r, i] == traj[r, j]`` (``traj``
+    None: every j <= i).  q/k/v: bf16 views whose element (token, h*64+d) sits at token*ld + h*64 + d, S tokens per row (the decoder's fused qkv rows); traj: int32
+    [rows, S] device tensor.  -> (out [rows * S, H * 64] bf16, lse [rows, H, S] fp32 or None).  64-wide heads, bf16, forward only; anything else, and S > 1024,
+    raises ``SvlaError`` (invalid argument) and launches nothing."""
+    _chk(q, BF16, "q")
+    if traj is not None:
+        _chk(traj, torch.int32, "traj")
+    W = H * head_dim
+    if out is None:
+        out = torch.empty(rows * S, W, device=q.device, dtype=BF16)
+    ldo = ldo if ldo is not None else out.stride(-2)
+    lse = torch.empty(rows, H, S, device=q.device, dtype=F32) if save_lse else None
+    lib().call("svla_attn_causal_fwd_bf16", _p(q), _p(k), _p(v), int(ld), _p(out), int(ldo), _p(lse), int(rows), int(S), int(H), int(head_dim), float(scale), _p(traj),
+               _stream())
+    return out, lse
+
+
 def swiglu_fwd(ab, M, Hd, out=None):
     if out is None:
         out = torch.empty(M, Hd, device=ab.device, dtype=ab.dtype)
