@@ -162,7 +162,7 @@ int svla_colsum_f32(const float* X, long ldx, int M, int N, int row_stride, floa
  * written by plain stores (bitwise repeatable).  Refused with SVLA_EINVAL, nothing launched: S > 512 (forward and backward, but see the next paragraph), bias with
  * S > 256 in the backward (the only biased attention, the frozen T5, has no backward).
  * head_dim 64, forward, 512 < S <= 1024: the single-query ("decode") form only -- Sq == 1, no bias, mask_mode 0, no dropout; kvalid [rows,S] or null, kv_rows >= S,
- * ldq, optional LSE [rows,H] (natural log) -- on csrc/attn_decode_long.hip: the KV-cached acting step of the llama decoder over a cache window of up to 1024 slots
+ * ldq, optional LSE [rows,H] (natural log) -- on csrc/attn_decode.hip: the KV-cached acting step of the llama decoder over a cache window of up to 1024 slots
  * (the reference's policies and llama caches are built for 1000 steps, its online evaluation runs episodes of 600 and 1000).  Only valid keys are read; a row without
  * a valid key yields zeros; the cost follows the number of 32-key blocks that hold a valid key, not S.  Every other form above 512 keys, and S > 1024, is SVLA_EINVAL
  * HERE; the causal sequence forward of a whole episode (all S queries, up to 1024 keys) is an entry of its own, svla_attn_causal_fwd_bf16 at the end of this header.
@@ -335,7 +335,7 @@ int svla_kv_append_rows_bf16(const svla_bf16* src, long ld_src, svla_bf16* cache
  * row cache_row[r] (NULL: r), kv_rows token rows per cache row, 1 <= kv_rows <= 1024.  With slot t mod W written at step t and klen = min(t + 1, W) the ring is the
  * sliding window over the last W embedded steps of early_fusion_tsfm_models.py:491-497.  Q row r at Q + r*ldq, K / V token rows ld apart, O [rows, ldo], LSE
  * [rows, H] (natural log) or NULL.  head_dim 64 only.  bf16 products, fp32 accumulation, probabilities rounded to bf16 before P V (the arithmetic of the
- * single-query forms of svla_attn_fwd_bf16); klen[r] <= 0: a zero row and -inf LSE.  The cost follows klen[r], not kv_rows (csrc/attn_decode_rows.hip).
+ * single-query forms of svla_attn_fwd_bf16); klen[r] <= 0: a zero row and -inf LSE.  The cost follows klen[r], not kv_rows (csrc/attn_decode.hip).
  * SVLA_EINVAL, nothing launched: rows or H <= 0, head_dim != 64, kv_rows outside 1..1024, ld, ldq or ldo not a multiple of 8, klen NULL. */
 int svla_attn_decode_rows_bf16(const svla_bf16* Q, long ldq, const svla_bf16* K, const svla_bf16* V, long ld, svla_bf16* O, long ldo, float* LSE, const int* klen,
                                const int* cache_row, int rows, int H, int head_dim, float scale, int kv_rows, void* stream);

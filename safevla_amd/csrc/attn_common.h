@@ -1,4 +1,4 @@
-// Device primitives shared by the attention translation units (attn.hip, attn_long.hip, attn_hd96.hip, attn_fp8.hip, attn_decode_long.hip).  Two of them are
+// Device primitives shared by the attention translation units (attn.hip, attn_long.hip, attn_hd96.hip, attn_fp8.hip, attn_decode.hip).  Two of them are
 // contracts between files: the dropout element index decides WHICH probabilities are dropped (forward, backward, the fp8 variant and the fp32 twin of f32.hip
 // must agree bit for bit), and the chunk swizzle is the LDS image that staging stores and both kinds of fragment read share.  A new attention kernel includes
 // this header; it does not copy from it.

@@ -27,7 +27,7 @@ struct AttnCall {
     hipStream_t stream;
 };
 
-#define DECL_MAXS 1024      // keys of the longest cache window (the LDS arrays of attn_decode_long.hip)
+#define DEC_MAXS 1024      // keys of the longest cache window or KV ring (the LDS score arrays of attn_decode.hip)
 
 // What one kernel family takes.  Every family also needs rows, H > 0, 0 <= Sq <= S, ld % 8 == 0, lddo % 8 == 0, Sq > 0 ? ldq % 8 == 0, kv_rows <= 0 or >= S, and
 // traj with the block-causal mask.  (A stride the call does not have is 0 and passes any multiple.)
@@ -38,9 +38,9 @@ struct AttnLimits {
     int ldo_mult, ldd_mult, lddq_mult;
 };
 //                                                   S              bias   masks  ldo ldd lddq
-constexpr AttnLimits ATTN_FWD_64          = {  1,       512, true,  false, 1, 1, 1};      // attn.hip: tile and decode kernels
-constexpr AttnLimits ATTN_FWD_64_DECODE_L = {513, DECL_MAXS, false, true,  1, 1, 1};      // attn_decode_long.hip; the entry also asks for Sq == 1, no mask, no dropout
-constexpr AttnLimits ATTN_FWD_64_CAUSAL_L = {  1, DECL_MAXS, false, true,  8, 1, 1};      // attn_seq_long.hip: its own entry (svla_attn_causal_fwd_bf16), which also asks for ld, ldo >= H * 64
+constexpr AttnLimits ATTN_FWD_64          = {  1,       512, true,  false, 1, 1, 1};      // attn.hip: the tile kernels
+constexpr AttnLimits ATTN_FWD_64_DECODE   = {  1,  DEC_MAXS, false, true,  1, 1, 1};      // attn_decode.hip: what svla_attn_fwd_bf16 routes there (one query, no bias / mask / dropout)
+constexpr AttnLimits ATTN_FWD_64_CAUSAL_L = {  1,  DEC_MAXS, false, true,  8, 1, 1};      // attn_seq_long.hip: its own entry (svla_attn_causal_fwd_bf16), which also asks for ld, ldo >= H * 64
 constexpr AttnLimits ATTN_FWD_96          = {  1,       256, false, true,  4, 1, 1};      // attn_hd96.hip
 constexpr AttnLimits ATTN_BWD_64          = {  1,       256, true,  false, 1, 1, 8};      // attn.hip
 constexpr AttnLimits ATTN_BWD_64_LONG     = {257,       512, false, true,  8, 4, 4};      // attn_long.hip
@@ -77,4 +77,4 @@ template <int N0, int... N, class F> inline int attn_bucket(int S, F&& f) {
 int attn96_fwd_launch(const AttnCall& c);            // attn_hd96.hip: head_dim 96
 int attn96_bwd_launch(const AttnCall& c);
 int attn_long_bwd_launch(const AttnCall& c);         // attn_long.hip: head_dim 64, 256 < S <= 512 (D_ws is accepted and unused: the dK/dV kernel computes D itself)
-int attn_decode_long_launch(const AttnCall& c);      // attn_decode_long.hip: head_dim 64, one query, 512 < S <= DECL_MAXS
+int attn_decode_launch(const AttnCall& c);           // attn_decode.hip: head_dim 64, one query, S <= DEC_MAXS

@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(256) attn_fwd_f32_kernel(AttnF32Args p) {
     }
 }
 
-// Single-query forward over a KV-cache window of AF_MAXS < S <= AF_DEC_MAXS keys (the fp32 twin of csrc/attn_decode_long.hip: Sq == 1, 64-wide heads, no bias /
+// Single-query forward over a KV-cache window of AF_MAXS < S <= AF_DEC_MAXS keys (the fp32 twin of csrc/attn_decode.hip: Sq == 1, 64-wide heads, no bias /
 // trajectory mask / dropout): the whole workgroup works on the one query of its (row, head) -- thread t scores keys t, t + 256, ..., then wave w sums P.V over keys
 // w, w + 4, ....  Masked keys are not read.  Same definitions as attn_fwd_f32_kernel (softmax in fp32, LSE = -inf and a zero row when no key is valid).
 #define AF_DEC_MAXS 1024

@@ -275,7 +275,7 @@ class EarlyFusionCnnTransformerAgent:
     for the SigLIP presets any callable ``tokenizer([text], context_length=64) -> ids [1, 64]`` like open_clip's; neither vocabulary ships offline) or already
     tokenised ids (``{"input_ids", "attention_mask"}`` / an id tensor).  ``max_seq_len`` = the KV-cache window: 1000 by default, the reference's
     (early_fusion_tsfm_models.py:370; its online evaluation runs episodes of 600 steps, 1000 for RoomVisit / ObjectNavMulti), capped at the 1024 keys of the
-    single-query attention kernels (csrc/attn_decode_long.hip) and at the model's ``max_steps``: every step attends to all steps of the episode so far, as the
+    single-query attention kernels (csrc/attn_decode.hip) and at the model's ``max_steps``: every step attends to all steps of the episode so far, as the
     reference's llama path does.  Only an episode that outlives that window restarts it, with a warning (the reference's llama caches end at 1000
     steps too)."""
 

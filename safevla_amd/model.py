@@ -196,7 +196,7 @@ class Tower(nn.Module):
         self.arena = arena
         self.device_ = device
         if not 1 <= int(max_steps) <= MAX_ACTING_WINDOW:
-            # the KV-cache window of the acting step: the single-query attention kernels end at 1024 keys (csrc/attn_decode_long.hip; the reference's policies and
+            # the KV-cache window of the acting step: the single-query attention kernels end at 1024 keys (csrc/attn_decode.hip; the reference's policies and
             # llama caches are built for 1000).  Refused here, not by a kernel status at step 1024 -- or, on the recorded path (S = max_steps), at the first step
             raise ValueError(f"max_steps = {max_steps}: the KV-cache window of the acting step is limited to {MAX_ACTING_WINDOW} steps")
         self.max_steps = max_steps

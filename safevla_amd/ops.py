@@ -447,7 +447,7 @@ def attn_fwd(q, k, v, ld, rows, S, H, scale, out=None, ldo=None, mask_mode=MASK_
     every row (q then holds Sq rows per batch row with row stride ldq).
 
     Key counts: S <= 512, except the single-query form of the KV-cached acting step -- ``Sq == 1``, ``head_dim`` 64, no ``bias``, no ``traj`` mask, no ``drop`` -- which
-    takes S <= 1024 (bf16: csrc/attn_decode_long.hip; fp32: its twin in csrc/f32.hip): ``kvalid`` [rows, S] or None, ``kv_rows`` >= S, ``ldq``, ``save_lse``.  It reads
+    takes S <= 1024 (bf16: csrc/attn_decode.hip; fp32: its twin in csrc/f32.hip): ``kvalid`` [rows, S] or None, ``kv_rows`` >= S, ``ldq``, ``save_lse``.  It reads
     only the valid keys, so a step costs what its episode's length costs, whatever the window.  Any other form above 512 keys, and S > 1024, raises ``SvlaError``
     (invalid argument) and launches nothing.
 
@@ -689,7 +689,7 @@ def kv_append_rows(src, ld_src, cache, cache_row, pos, rows, width):
 
 
 def attn_decode_rows(q, ldq, k, v, ld, klen, cache_row, rows, H, scale, kv_rows, out=None, ldo=None, save_lse=False, head_dim=64):
-    """One query per row against that row's own KV ring (csrc/attn_decode_rows.hip): row r reads keys [0, min(klen[r], kv_rows)) of cache row cache_row[r] (None: r),
+    """One query per row against that row's own KV ring (csrc/attn_decode.hip): row r reads keys [0, min(klen[r], kv_rows)) of cache row cache_row[r] (None: r),
     ``kv_rows`` (<= 1024) token rows per cache row.  klen, cache_row: int32 [rows] device tensors.  -> (out [rows, H * 64] bf16, lse [rows, H] fp32 or None); a row
     with klen <= 0 comes out as zeros.  64-wide heads, bf16 only; anything else raises ``SvlaError`` (invalid argument) and launches nothing."""
     _chk(q, BF16, "q")

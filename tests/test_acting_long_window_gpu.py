@@ -1,4 +1,4 @@
-"""Acting through episodes longer than 512 steps: the KV-cached policy step over a cache window of up to 1024 slots (csrc/attn_decode_long.hip), on the plain,
+"""Acting through episodes longer than 512 steps: the KV-cached policy step over a cache window of up to 1024 slots (csrc/attn_decode.hip), on the plain,
 the recorded and the tower-grouped acting paths of the three-tower model, in the fp32 verification mode, and in the imitation-learning model's online agent.
 
 The reference evaluates online on episodes of 600 steps (1000 for RoomVisit / ObjectNavMulti) and builds its policies and llama caches for 1000; every step

@@ -43,6 +43,8 @@ FWD = [
     dict(mask_mode=BLOCK_CAUSAL), dict(Sq=65), dict(kv_rows=10),
     dict(HD96, S=300), dict(HD96, bias=PTR), dict(HD96, mask_mode=2), dict(HD96, ldo=770),  # 96-wide
     dict(S=1025, Sq=1, ldq=512), dict(S=600, Sq=1, ldq=512, bias=PTR),                      # single-query decode above 512 keys
+    dict(S=600, Sq=1, ldq=512, mask_mode=2), dict(S=600, Sq=1, ldq=516), dict(S=600, Sq=1, ldq=512, kv_rows=599),
+    dict(S=600, Sq=2, ldq=512),                                                             # more than one query: no form above 512 keys
 ]
 BWD_64 = [
     dict(rows=0), dict(H=0), dict(S=0), dict(S=513), dict(head_dim=80), dict(ld=1540), dict(lddo=516),

@@ -1,5 +1,5 @@
 """Register / spill / LDS budget of the streaming causal attention forward (csrc/attn_seq_long.hip), checked at compile time (hipcc cross-compiles gfx950 without a
-GPU; the mechanism of tests/test_kernel_resources_cpu.py, the pattern of tests/test_attn_decode_rows_resources_cpu.py).
+GPU; the mechanism of tests/test_kernel_resources_cpu.py, the pattern of tests/test_attn_decode_resources_cpu.py).
 
 The kernel and its grouped twin must not spill or use scratch; their LDS (all of it static: two K + V tile buffers and the trajectory ids, no dynamic part) must let
 two workgroups share a CU's 160 KiB; and they stay at or below the 117 VGPRs both compiled to on 2026-10-20 (four workgroups of four waves per CU)."""

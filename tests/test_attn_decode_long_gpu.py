@@ -1,4 +1,4 @@
-"""Single-query ("decode") attention over a KV-cache window of 512 < S <= 1024 keys (csrc/attn_decode_long.hip behind svla_attn_fwd_bf16, its fp32 twin behind
+"""Single-query ("decode") attention over a KV-cache window of 512 < S <= 1024 keys (csrc/attn_decode.hip behind svla_attn_fwd_bf16, its fp32 twin behind
 svla_attn_fwd_f32): the acting step of the llama decoder on episodes of up to 1000 steps, the length the reference's online evaluation runs.
 
 Reference: fp64 torch on the CPU from the same bf16 inputs, masked softmax over ``kvalid``, probabilities rounded to bf16 before P.V (the kernel's arithmetic:

@@ -1,4 +1,4 @@
-"""What svla_attn_decode_rows_bf16 / svla_kv_append_rows_bf16 (include/svla.h, csrc/attn_decode_rows.hip) refuse: host checks that return SVLA_EINVAL (-1) before any
+"""What svla_attn_decode_rows_bf16 / svla_kv_append_rows_bf16 (include/svla.h, csrc/attn_decode.hip) refuse: host checks that return SVLA_EINVAL (-1) before any
 launch, so they hold on a machine without a GPU (the mechanism of tests/test_attn_cabi_cpu.py; the GPU side, with outputs that stay untouched, is in
 tests/test_attn_decode_rows_gpu.py)."""
 import ctypes

@@ -1,4 +1,4 @@
-"""Per-row KV rings through the C ABI (csrc/attn_decode_rows.hip): svla_attn_decode_rows_bf16 -- one query per row over the prefix [0, min(klen[r], kv_rows)) of
+"""Per-row KV rings through the C ABI (csrc/attn_decode.hip): svla_attn_decode_rows_bf16 -- one query per row over the prefix [0, min(klen[r], kv_rows)) of
 cache row cache_row[r] -- and svla_kv_append_rows_bf16 -- cache[cache_row[r], pos[r]] = src[r].
 
 Reference of the attention: the fp64 torch computation of tests/test_attn_decode_long_gpu.py (from the same bf16 inputs, masked softmax, probabilities rounded to
@@ -103,6 +103,26 @@ def test_decode_rows_vs_fp64_and_the_kvalid_form(ops, W, H, permuted):
         if empty.any():
             assert (o.float().cpu().view(ROWS, H, HD)[empty] == 0).all(), name
             assert not torch.isfinite(got_lse[empty]).any(), name
+
+
+@pytest.mark.parametrize("S", [33, 512, 513, 1024])
+def test_a_prefix_gives_the_same_bits_through_every_kernel(ops, S):
+    """The three kernels share their arithmetic (csrc/attn_decode.hip: the dec_* helpers) and add in the same order, so a prefix of n keys comes out bit for bit
+    the same through attn_decode_rows (klen = n) and through attn_fwd with a prefix kvalid (S <= 512: attn_decode_kernel, above: attn_decode_long_kernel)."""
+    rows, H = 4, 2
+    D = H * HD
+    kv, q = rnd(rows * S, 2 * D, seed=300 + S).bfloat16().to(DEV), rnd(rows, 3 * D, seed=301 + S).bfloat16().to(DEV)
+    for n in (1, 32, 33, S):
+        klen = torch.full((rows,), n, dtype=torch.int32, device=DEV)
+        kvalid = torch.zeros(rows, S, dtype=torch.uint8, device=DEV)
+        kvalid[:, :n] = 1
+        o, lse = ops.attn_decode_rows(q, 3 * D, kv, kv[:, D:], 2 * D, klen, None, rows, H, 0.125, S, save_lse=True)
+        o2, lse2 = ops.attn_fwd(q, kv, kv[:, D:], 2 * D, rows, S, H, 0.125, kvalid=kvalid, save_lse=True, Sq=1, ldq=3 * D, kv_rows=S)
+        torch.cuda.synchronize()
+        print(f"S={S} n={n}: max |dO| {float((o.float() - o2.float()).abs().max()):.3e}, max |dLSE| {float((lse.view(-1) - lse2.view(-1)).abs().max()):.3e}")
+        assert torch.isfinite(lse).all() and (o.float().abs().sum(-1) > 0).all(), (S, n)
+        assert torch.equal(o, o2), (S, n)
+        assert torch.equal(lse.view(-1), lse2.view(-1)), (S, n)
 
 
 def test_negative_klen_is_an_empty_row(ops):

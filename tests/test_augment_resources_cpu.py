@@ -1,5 +1,5 @@
 """Register / scratch / LDS figures of the frame-augmentation kernels (csrc/augment.hip), read from the compiled gfx950 code object (hipcc cross-compiles without a
-GPU; the mechanism of tests/test_decode_long_resources_cpu.py).
+GPU; the mechanism of tests/test_attn_decode_resources_cpu.py).
 
 The three kernels index no array dynamically (operation codes, factors and blur weights are scalar kernel arguments selected by unrolled code), so none may use
 scratch; their LDS is static: the staged chunk of the gray reduction, the jitter tile with its blur halo, the crop source rectangle plus the resized tile with its

@@ -1,5 +1,5 @@
 """``EarlyFusionCnnTransformerVectorAgent``: several online episodes of the imitation-learning model on per-row KV rings behind one set of weights
-(safevla_amd/il.py; csrc/attn_decode_rows.hip; the fusion encoder's key-padding mask).
+(safevla_amd/il.py; csrc/attn_decode.hip; the fusion encoder's key-padding mask).
 
 Reference of every check: ``forward(batch)`` of the same model on ONE episode alone (B = 1, its goal unpadded, ``last_actions`` = the agent's own actions shifted,
 start token first) -- the comparison of tests/test_il_gpu.py::test_il_agent_steps_equal_full_sequence_forward, and its gate: 2e-2 * max(ref.max(), 1e-3) on the

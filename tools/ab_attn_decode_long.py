@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B of the single-query ("decode") attention forward over long KV-cache windows (csrc/attn_decode_long.hip: head_dim 64, 512 < S <= 1024) against the kernel for
-S <= 512 (csrc/attn.hip: attn_decode_kernel), per launch at rows = 64 and rows = 1 with H = 8:
+"""A/B of the single-query ("decode") attention forward over long KV-cache windows (csrc/attn_decode.hip: attn_decode_long_kernel, head_dim 64, 512 < S <= 1024) against the kernel for
+S <= 512 (attn_decode_kernel of the same file), per launch at rows = 64 and rows = 1 with H = 8:
   baseline  S = 500, all 500 keys valid, and S = 500 with a 100-key window (run this file on the previous revision for the baseline of record: the S > 512 lines then
             print 'refused');
   long      S = 1000 with 1000 valid keys (twice the bytes of the baseline) and S = 1000 with a 100-key window at slots 850 .. 949 (what the recorded acting path

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""A/B of the vector IL agent (safevla_amd/il.py: EarlyFusionCnnTransformerVectorAgent on per-row KV rings, csrc/attn_decode_rows.hip), one process, HIP events,
+"""A/B of the vector IL agent (safevla_amd/il.py: EarlyFusionCnnTransformerVectorAgent on per-row KV rings, csrc/attn_decode.hip), one process, HIP events,
 5 warm-up calls and 20 repetitions per figure (``--reps``); median, min and max of the repetitions are printed.
-  (a) kernel  ops.attn_decode_rows against ops.attn_fwd with a prefix ``kvalid`` (csrc/attn_decode_long.hip) at 64 rows x 8 heads, window 1000, with 100 and with
+  (a) kernel  ops.attn_decode_rows against ops.attn_fwd with a prefix ``kvalid`` (attn_decode_long_kernel of the same file) at 64 rows x 8 heads, window 1000, with 100 and with
               1000 valid keys.  As in tools/ab_attn_decode_long.py every launch works on one of nine caches in turn (1.2 GB: more than the last-level cache
               holds); a repetition is 45 launches (five rounds over the caches), and the two kernels alternate repetition by repetition.
   (b) agent   N single agents (one model copy each, as the reference's evaluation workers hold) stepped in turn against ONE vector agent of N slots, N = 1, 8, 32:
