@@ -74,7 +74,13 @@ int svla_small_linear_bwd_f32(const float* x, const float* W, const float* dout,
 /* LayerNorm (rms=0) / RMSNorm (rms=1) rows of width D.  Forward widths 384 / 512 / 768 / 1024 (frozen ViT-S / policy / ViT-B + SigLIP-B + the 768-wide IL presets / ViT-L), backward 512 / 768.  Row maps (G,GS,OFF): logical row m is
  * memory row (m/G)*GS + OFF + m%G (G = 0: identity).  Optional fused ReLU and per-group token add: the
  * "Linear -> LayerNorm -> ReLU (+ camera token)" adapters (allenact_dino_transformer.py:509-513,539-543,672-688);
- * nn.TransformerEncoderLayer norm1/norm2 (:545-552); llama RMSNorm (training/online/third_party_models/llama/model.py:28-71). */
+ * nn.TransformerEncoderLayer norm1/norm2 (:545-552); llama RMSNorm (training/online/third_party_models/llama/model.py:28-71).
+ * Backward: `mean` is required unless rms (the forward saves none for an RMSNorm).  The gradient outputs dgamma / dbeta / dtok ACCUMULATE (+=) into what the
+ * caller left in them; each may be NULL.  dtok is [2, D] at most: the token group of row m is (dyG > 0 ? m % dyG : m) / tok_group, and a call with more than two
+ * groups (G_eff > 2 * tok_group, G_eff = dyG > 0 ? dyG : rows) is SVLA_EINVAL -- the forward's tok takes any number of groups.  dres (added to dx) and dx_drop
+ * (dx under the keep mask / scale of `drop`, element index m * row_mult * D + col) are contiguous [rows, D] and take no row map; so are mean / rstd [rows].
+ * SVLA_EINVAL before anything is launched: rows <= 0, a width that is not built, a NULL x / gamma / y (forward) or dy / x / gamma / rstd / dx (backward),
+ * mean == NULL with rms == 0 (backward), a row map with G < 0, tok / dtok with tok_group <= 0, more than two dtok groups. */
 int svla_norm_fwd_bf16(const svla_bf16* x, int xG, int xGS, int xOFF, const float* gamma, const float* beta, float eps, int rows,
                        int D, int rms, int relu, const float* tok, int tok_group, svla_bf16* y, int yG, int yGS, int yOFF,
                        float* mean, float* rstd, void* stream);

@@ -217,6 +217,8 @@ template <typename T>
 static int norm_fwd_launch(const T* x, int xG, int xGS, int xOFF, const float* gamma, const float* beta, float eps, int rows, int D, int rms,
                            int relu, const float* tok, int tok_group, T* y, int yG, int yGS, int yOFF, float* mean, float* rstd, void* stream) {
     if (rows <= 0) return SVLA_EINVAL;
+    if (!x || !gamma || !y) return SVLA_EINVAL;
+    if (xG < 0 || yG < 0) return SVLA_EINVAL;
     if (tok && tok_group <= 0) return SVLA_EINVAL;
     RowMap xm{xG, xGS, xOFF}, ym{yG, yGS, yOFF};
     dim3 grid(norm_grid(rows, 2048)), block(256);
@@ -236,7 +238,12 @@ static int norm_bwd_launch(const T* dy, int dyG, int dyGS, int dyOFF, const T* x
                            const T* dres, T* dx, int dxG, int dxGS, int dxOFF, float* dgamma, float* dbeta, float* dtok, T* dx_drop,
                            const svla_dropout* drop, void* stream) {
     if (rows <= 0 || (D != 512 && D != 768)) return SVLA_EINVAL;
+    if (!dy || !x || !gamma || !rstd || !dx) return SVLA_EINVAL;
+    if (!rms && !mean) return SVLA_EINVAL;                                  // LayerNorm reads mean[m]
+    if (dyG < 0 || xG < 0 || dxG < 0) return SVLA_EINVAL;
     if (dtok && tok_group <= 0) return SVLA_EINVAL;
+    // the kernel keeps two token-group accumulators and writes dtok[0 .. 2D): group index = (dyG > 0 ? m % dyG : m) / tok_group must stay below 2
+    if (dtok && (long)(dyG > 0 ? dyG : rows) > 2L * tok_group) return SVLA_EINVAL;
     RowMap dym{dyG, dyGS, dyOFF}, xm{xG, xGS, xOFF}, dxm{dxG, dxGS, dxOFF};
     const int blocks = norm_grid(rows, 4096);   // measured (tools/norm_bw.py, 2.97 M rows): 5.09 TB/s at 1 024 workgroups, 5.23 at 4 096 (each ends with up to 4*D atomics)
 #define NORM_BWD_CASE(DD) hipLaunchKernelGGL((norm_bwd_kernel<T, DD>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, dym, x, xm, gamma, beta, mean, \

@@ -720,7 +720,7 @@ def test_invalid_arguments_are_refused_not_computed(ops):
     with pytest.raises(SvlaError):
         ops.attn_fwd(qkv, qkv[:, 64:], qkv[:, 128:], 192, 2, 16, 1, 0.125, mask_mode=ops.MASK_BLOCK_CAUSAL)   # block-causal without traj ids
     with pytest.raises(SvlaError):
-        ops.norm_fwd(torch.zeros(4, 256, device=DEV, dtype=bf), torch.ones(256, device=DEV), None, 1e-5, 4, D=256)  # only D = 384 / 512 are built
+        ops.norm_fwd(torch.zeros(4, 256, device=DEV, dtype=bf), torch.ones(256, device=DEV), None, 1e-5, 4, D=256)  # forward widths built: 384 / 512 / 768 / 1024
     with pytest.raises((ValueError, TypeError)):
         ops.gemm_nt(A.float(), W, 64, 128, 64)                     # wrong dtype is caught before the C call
 
