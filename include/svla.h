@@ -513,6 +513,25 @@ int svla_swiglu_bwd_f32(const float* ab, const float* dg, long M, int Hd, float*
 int svla_embed_gather_f32(const float* table, const int64_t* ids, long n, int D, float* out, void* stream);
 int svla_dropout_f32(float* x, long rows, int N, const svla_dropout* drop, void* stream);
 
+/* ---- policy read-out of an acting step ----------------------------------------------------------------------------------------------
+ * (Declared in front of the last section, which tests/test_attn_causal_long_cabi_cpu.py keeps last: of the existing entries only svla_attn_causal_fwd_bf16 moves, by one.
+ * The ids of svla_replay_calls are derived from this header at build time and at load time alike, and the stamp of svla_replay_abi_stamp ties the two together.)
+ * What an agent does with the actor's logits -- distributions.sample() / .mode() / .probs of inference_agent.py:276-278 on AllenAct's CategoricalDistr [3P]:
+ * log_softmax, exp, multinomial, argmax -- in one launch (csrc/sample.hip), one wave per row, with a draw that is a pure function of (seed, slot, age) instead of
+ * a shared generator's state: a row's sampled action does not depend on which other rows share the launch.  logits [n, A] fp32, rows ld apart; slot, age int32 [n]
+ * in device memory; outputs log_probs, probs [n, A] fp32 (contiguous), sampled, greedy int32 [n].  For every row:
+ *   log_probs[k] = logits[k] - (m + log(sum_j exp(logits[j] - m))), m = max_j logits[j], in fp32;     probs[k] = exp(log_probs[k]);
+ *   greedy  = the lowest index k with logits[k] == m;
+ *   h       = mix24(seed ^ (uint32)slot * 0x9E3779B1);   r = mix24(h ^ (uint32)age * 0x85EBCA77 ^ 0xC2B2AE3D) >> 8;   u = r * 2^-24  (24 bits: exact in fp32;
+ *             mix24 as defined for svla_dropout above, all arithmetic mod 2^32, seed taken as its 32 bits);
+ *   c_k     = probs[0] + ... + probs[k], fp32, added one by one in action order, over the values written to probs;
+ *   sampled = the smallest k with c_k > u * c_{A-1} (one fp32 multiply) and probs[k] > 0; if there is none, the last k with probs[k] > 0.
+ * An action whose probability is exactly 0 is therefore never sampled (mask_non_nav_actions: a bias of -999999 underflows to probability 0).  Only a row without
+ * any probs[k] > 0 (NaN logits) returns sampled = greedy.  Plain stores, no atomics: two launches with the same arguments are bitwise equal.
+ * SVLA_EINVAL, nothing launched: n <= 0, A < 1 or A > 64, ld < A, a NULL logits, slot, age or output. */
+int svla_policy_sample_rows_f32(const float* logits, long ld, const int* slot, const int* age, int seed, int n, int A, float* log_probs, float* probs,
+                                int* sampled, int* greedy, void* stream);
+
 /* ---- causal attention over whole episodes ----------------------------------------------------------------------------------------
  * (Declared last: svla_replay_calls numbers the entry points in declaration order, and a new one must not move the others.)
  * The sequence form of the llama decoder's attention (llama/model.py:249-322 with the block-causal traj_index mask of early_fusion_tsfm_models.py:160-178, 491-497)

@@ -7,6 +7,9 @@ Mirrors ``InferenceAgentVIDA`` (/root/reference/architecture/models/allenact_tra
 sample / mode.  The rollout storage is used exactly as the reference uses it (``initialize`` on the first step of a task, ``add``
 with dummy value/reward fields afterwards, ``agent_input_for_next_step``), so the prev-action / mask / time-step plumbing is the
 update path's own.
+
+``VectorInferenceAgentVIDA`` (``InferenceAgentVIDA.build_vector_agent``) serves many such episodes at once behind one set of weights: actor tower only, per-row KV
+rings, one-launch sampling.
 """
 import json
 import os
@@ -81,6 +84,30 @@ class InferenceAgentVIDA(AbstractAgent):
         ``vit_weights`` = path of a DINOv2 ViT-S/14 ``state_dict`` (hub names).  A Lightning IL checkpoint that carries its image
         encoder (``model.visual_encoder.image_encoder.model.*``) fills the ViT from there.  Running real weights on the offline
         stand-ins (word-hash token ids, random-init ViT) produces meaningless actions, so that combination WARNS loudly."""
+        vit_sd = cls._load_assets(actor_critic, ckpt_path, spiece_model, vit_weights)
+        agent = cls(actor_critic, device=device, greedy_sampling=greedy_sampling, **kw)
+        cls._load_vit(agent, vit_sd)
+        cls._warn_stand_ins(actor_critic, ckpt_path, vit_sd, kw)
+        agent.reset()
+        return agent
+
+    @classmethod
+    def build_vector_agent(cls, actor_critic, num_episodes: int = 1, device="cuda", greedy_sampling: bool = False, ckpt_path: Optional[str] = None,
+                           spiece_model: Optional[str] = None, vit_weights: Optional[str] = None, **kw):
+        """The same policy behind ``VectorInferenceAgentVIDA``: ``num_episodes`` evaluation episodes served by one set of weights, the actor tower only.  Checkpoint,
+        ``spiece_model`` and ``vit_weights`` as in ``build_agent``; ``kw``: ``seed``, ``nav_preprocessor``, ``manip_preprocessor``."""
+        vit_sd = cls._load_assets(actor_critic, ckpt_path, spiece_model, vit_weights)
+        agent = VectorInferenceAgentVIDA(actor_critic, num_episodes, device=device, greedy_sampling=greedy_sampling, **kw)
+        if vit_sd is not None:                  # (without weights to load the frozen ViT is built by the first raw frame: pre-encoded features need none)
+            agent._preprocessors()
+            cls._load_vit(agent, vit_sd)
+        cls._warn_stand_ins(actor_critic, ckpt_path, vit_sd, kw)
+        return agent
+
+    # ---- what build_agent and build_vector_agent share ------------------------------------------------------------------------------
+    @classmethod
+    def _load_assets(cls, actor_critic, ckpt_path, spiece_model, vit_weights):
+        """checkpoint -> the policy, ``spiece_model`` -> its tokenizer, eval mode; -> the state dict for the frozen ViT (from the checkpoint or ``vit_weights``) or None"""
         vit_sd = None
         if ckpt_path is not None:
             ckpt = torch.load(ckpt_path, map_location="cpu")
@@ -102,26 +129,32 @@ class InferenceAgentVIDA(AbstractAgent):
         if vit_weights is not None:
             vit_sd = torch.load(vit_weights, map_location="cpu")
         actor_critic.eval()     # AllenAct's InferenceAgent runs the policy in eval mode (mode="test", inference_agent.py:98-102)
-        agent = cls(actor_critic, device=device, greedy_sampling=greedy_sampling, **kw)
-        if vit_sd is not None:
-            missing, unexpected = agent.nav_pre.vit.load_state_dict(vit_sd, strict=False)
-            if missing:
-                warnings.warn(f"DINOv2 weights: {len(missing)} tensors not found (e.g. {missing[:3]}); those stay random-init")
-            agent.nav_pre.vit.sync()
-            if agent.manip_pre is not None and agent.manip_pre.vit is not agent.nav_pre.vit:
-                agent.manip_pre.vit.load_state_dict(vit_sd, strict=False)
-                agent.manip_pre.vit.sync()
-        if ckpt_path is not None:
-            stand_ins = []
-            if getattr(actor_critic.tokenizer, "_sp", None) is None:
-                stand_ins.append("word-hash goal tokenizer (pass spiece_model=<t5-small spiece.model>)")
-            if vit_sd is None and kw.get("nav_preprocessor") is None:
-                stand_ins.append("random-init DINOv2 ViT (pass vit_weights=<dinov2_vits14 state_dict>)")
-            if stand_ins:
-                warnings.warn("checkpoint loaded but offline stand-ins are active: " + "; ".join(stand_ins) +
-                              " -- the policy's inputs do not match what it was trained on, actions are meaningless", RuntimeWarning)
-        agent.reset()
-        return agent
+        return vit_sd
+
+    @staticmethod
+    def _load_vit(agent, vit_sd):
+        if vit_sd is None:
+            return
+        missing, unexpected = agent.nav_pre.vit.load_state_dict(vit_sd, strict=False)
+        if missing:
+            warnings.warn(f"DINOv2 weights: {len(missing)} tensors not found (e.g. {missing[:3]}); those stay random-init")
+        agent.nav_pre.vit.sync()
+        if agent.manip_pre is not None and agent.manip_pre.vit is not agent.nav_pre.vit:
+            agent.manip_pre.vit.load_state_dict(vit_sd, strict=False)
+            agent.manip_pre.vit.sync()
+
+    @staticmethod
+    def _warn_stand_ins(actor_critic, ckpt_path, vit_sd, kw):
+        if ckpt_path is None:
+            return
+        stand_ins = []
+        if getattr(actor_critic.tokenizer, "_sp", None) is None:
+            stand_ins.append("word-hash goal tokenizer (pass spiece_model=<t5-small spiece.model>)")
+        if vit_sd is None and kw.get("nav_preprocessor") is None:
+            stand_ins.append("random-init DINOv2 ViT (pass vit_weights=<dinov2_vits14 state_dict>)")
+        if stand_ins:
+            warnings.warn("checkpoint loaded but offline stand-ins are active: " + "; ".join(stand_ins) +
+                          " -- the policy's inputs do not match what it was trained on, actions are meaningless", RuntimeWarning)
 
     # ---- AbstractAgent ------------------------------------------------------------------------------------------------------
     def reset(self):
@@ -192,3 +225,171 @@ class InferenceAgentVIDA(AbstractAgent):
             st.after_updates()
         idx = int((greedy if self.greedy_sampling else sampled).reshape(-1)[0])
         return self.get_action_list()[idx], dist.probs[0][0]
+
+
+class VectorInferenceAgentVIDA:
+    """``num_episodes`` online evaluation episodes of the RL policy behind one set of weights: what ``InferenceAgentVIDA`` does for one episode, for a vector of
+    them that start, end and stall independently -- the evaluation workers of the reference (online_evaluation/) hold one model copy each.  ``reset(slot, goal_spec)``
+    starts an episode in a slot; ``get_actions({slot: frame})`` steps any non-empty subset of the started slots as ONE compact batch and returns
+    ``{slot: (action_str, action_probs[20])}``; slots that are absent keep their cache and their age.
+
+    Only the actor tower runs (``Tower.run_forward`` on the policy itself): evaluation reads the action distribution alone, so ``critic_tsfm`` and ``c_critic_tsfm`` --
+    two thirds of a single agent's step -- are never launched.  bf16 only, eval mode.
+
+    Per row the policy sees what ``InferenceAgentVIDA`` feeds it: ``time_step`` = the slot's age, the previous action = the action SAMPLED at the slot's last step (also
+    when acting greedily), ``masks`` = 0 on the slot's first step and 1 afterwards, the in-hand sensor and the manipulation camera only if the model has them.  A frame
+    carries raw uint8 camera frames under the evaluator's names (``raw_navigation_camera`` [, ``raw_manipulation_camera``]; one batched pass of the frozen ViT per
+    camera and call) or already-encoded features [384, 7, 12] under the model's own ``uuids["nav"]`` / ``uuids["manip"]``; ``an_object_is_in_hand`` as the single agent.
+
+    Slot s owns row s of the actor tower's llama KV caches, a ring of W = ``actor_critic.max_steps`` slots.  The RL reference has no sliding window: it restarts its
+    cache when its step counter reaches ``max_steps`` (allenact_dino_transformer.py:376-377), so a step of age a writes ring slot a % W and reads the a % W + 1 first
+    slots; an episode that reaches W steps restarts its window (one warning per agent, as the single agents warn) while ``time_step`` keeps counting.  Goals of
+    different lengths are right-padded to the longest; the padding is masked in T5 and hidden from every fusion layer (``Prep.fusion_kvalid``), and the action is
+    drawn by ``ops.policy_sample_rows`` from a counter (seed, slot, age) -- an episode's probabilities and sampled actions do not depend on which other slots share
+    its batch.  The frozen T5 reruns only when a ``reset`` brought a different goal.
+
+    One kind of agent on a model at a time: the cache rows are the tower's own, shared with the single agent and the rollout path (which write row 0 ... B - 1 at the
+    tower's step counter), so stepping either in between overwrites the slots' histories.  The tower's step counter is neither read nor advanced here; when the vector
+    agent has to reallocate the caches, every recorded acting plan is dropped (``invalidate_recorded``)."""
+
+    RAW_CAMERAS = ("raw_navigation_camera", "raw_manipulation_camera")        # evaluator's names of the raw frames -> the inputs of nav_pre / manip_pre
+    _PRE_INPUTS = ("rgb_raw", "manipulation_rgb_raw")
+
+    def __init__(self, actor_critic, num_episodes: int, device="cuda", greedy_sampling: bool = False, nav_preprocessor=None, manip_preprocessor=None, seed: int = 0):
+        from .model import BF16
+        if not 1 <= int(num_episodes) <= 1024:
+            raise ValueError(f"num_episodes = {num_episodes}: 1 ... 1024 episodes per vector agent")
+        if actor_critic.adt != BF16:
+            raise NotImplementedError("precision='fp32': the acting step on per-row KV rings exists on the bf16 product path only")
+        self.actor_critic, self.device, self.greedy_sampling = actor_critic, torch.device(device), greedy_sampling
+        self.num_episodes, self.seed = int(num_episodes), int(seed)
+        self.window = actor_critic.max_steps
+        self.nav_pre, self.manip_pre = nav_preprocessor, manip_preprocessor
+        self._age = [None] * self.num_episodes                 # host-side: steps taken in the slot's episode (None: not started)
+        self._last = [0] * self.num_episodes                   # the action sampled at the slot's last step
+        self._goal_ids = [None] * self.num_episodes            # token ids without padding, as tuples
+        self._goals = None                                     # _goal_table() of the current goals; None: a goal changed
+        self._warned_window = False
+        actor_critic.eval()
+
+    get_action_list = InferenceAgentVIDA.get_action_list
+
+    def _preprocessors(self):
+        """the frozen ViT front of raw frames, built on first use (pre-encoded features never need it); one ViT serves both cameras, as in ``InferenceAgentVIDA``"""
+        u = self.actor_critic.uuids
+        shared = self.nav_pre is None and self.manip_pre is None
+        if self.nav_pre is None:
+            self.nav_pre = DinoViTPreprocessor(self._PRE_INPUTS[0], u["nav"], device=self.device)
+        if self.manip_pre is None and u["manip"] is not None:
+            self.manip_pre = DinoViTPreprocessor(self._PRE_INPUTS[1], u["manip"], device=self.device)
+            if shared:
+                self.manip_pre.vit = self.nav_pre.vit
+
+    def age(self, slot: int) -> int:
+        return self._age[self._started(slot)]
+
+    def _slot(self, slot) -> int:
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.num_episodes:
+            raise KeyError(slot)
+        return int(slot)
+
+    def _started(self, slot) -> int:
+        slot = self._slot(slot)
+        if self._age[slot] is None:
+            raise KeyError(slot)
+        return slot
+
+    def reset(self, slot: int, goal_spec):
+        """Start an episode in ``slot``.  ``goal_spec``: a string (tokenised here, once, with ``actor_critic.tokenizer``) or token ids -- ``{"input_ids"[,
+        "attention_mask"]}`` or an id sequence; right-padded ids keep their tokens"""
+        slot = self._slot(slot)
+        if isinstance(goal_spec, str):
+            ids = self.actor_critic.tokenizer.encode(goal_spec)
+        elif isinstance(goal_spec, dict):
+            ids = torch.as_tensor(goal_spec["input_ids"]).reshape(-1)
+            if "attention_mask" in goal_spec:
+                ids = ids[: int(torch.as_tensor(goal_spec["attention_mask"]).sum())]
+            ids = ids.tolist()
+        else:
+            ids = torch.as_tensor(goal_spec).reshape(-1).tolist()
+        ids = tuple(int(v) for v in ids)
+        if not ids:
+            raise ValueError("an empty goal")
+        if ids != self._goal_ids[slot]:
+            self._goal_ids[slot], self._goals = ids, None
+        self._age[slot], self._last[slot] = 0, 0
+
+    def _goal_table(self):
+        """-> (ids_key, ids [N, L] of all slots (row = slot, right-padded to the longest; a slot that never started holds one end-of-sequence token), the T5 padding
+        mask [N, L] as int64 and uint8, fusion key mask [N, S] uint8 or None without padding, goal length per slot, L); rebuilt when a goal changed"""
+        if self._goals is None:
+            dev, off = self.device, self.actor_critic.text_off
+            rows = [g if g is not None else (1,) for g in self._goal_ids]
+            lens = [len(g) for g in rows]
+            L = max(lens)
+            ids = torch.tensor([list(g) + [0] * (L - len(g)) for g in rows], dtype=torch.int64)
+            mask = torch.arange(L)[None, :] < torch.tensor(lens)[:, None]
+            kvalid = torch.cat([torch.ones(len(rows), off, dtype=torch.uint8), mask.to(torch.uint8)], 1).contiguous().to(dev) if min(lens) < L else None
+            self._goals = (("vector", tuple(rows)), ids.to(dev), mask.to(torch.int64).to(dev), mask.to(torch.uint8).to(dev), kvalid, lens, L)
+        return self._goals
+
+    def _features(self, obs, cam: int) -> torch.Tensor:
+        """camera ``cam`` of the call's frames -> features [n, 384, 7, 12] fp32: pre-encoded ones as they come, raw uint8 frames through ONE batched pass of the ViT"""
+        u, dev = self.actor_critic.uuids, self.device
+        feat_key, raw_key = (u["nav"], u["manip"])[cam], self.RAW_CAMERAS[cam]
+        stack = lambda key: torch.stack([o[key] if torch.is_tensor(o[key]) else torch.as_tensor(np.ascontiguousarray(o[key])) for o in obs]).to(dev)
+        if all(feat_key in o for o in obs):
+            return stack(feat_key).float()
+        self._preprocessors()
+        if cam == 1 and not all(raw_key in o for o in obs):      # a policy with the manipulation camera, an evaluator without: black frames, as the single agent
+            like = np.asarray(obs[0][self.RAW_CAMERAS[0]])
+            obs = [o if raw_key in o else {raw_key: np.zeros_like(like)} for o in obs]
+        return (self.nav_pre, self.manip_pre)[cam].process({self._PRE_INPUTS[cam]: stack(raw_key)})
+
+    @torch.no_grad()
+    def get_actions(self, frames: Dict[int, Dict[str, Any]]) -> Dict[int, Tuple[str, torch.Tensor]]:
+        from . import ops
+        from .model import F32, NPATCH, Prep
+        ac, dev = self.actor_critic, self.device
+        if not frames:
+            raise ValueError("get_actions needs the frames of at least one started slot")
+        slots = [self._started(s) for s in frames]
+        obs, n, W = list(frames.values()), len(frames), self.window
+        ages = [self._age[s] for s in slots]
+        if not self._warned_window and any(a and a % W == 0 for a in ages):
+            warnings.warn(f"episode longer than the {W}-step KV-cache window (max_steps): the window restarts, as the reference's step counter does")
+            self._warned_window = True
+        key, ids, am, am_u8, kvalid, lens, L = self._goal_table()
+        hand = [int(np.asarray(o.get("an_object_is_in_hand", 0)).reshape(-1)[0]) for o in obs] if ac.has_hand else [0] * n
+        # the step's one small upload, per row: cache row (= slot), ring slot to write, slots to read, age, previous action, in-hand sensor
+        rows = torch.tensor([slots, [a % W for a in ages], [a % W + 1 for a in ages], ages, [self._last[s] for s in slots], hand], dtype=torch.int32).to(dev)
+        p = Prep()
+        p.T, p.B, p.R = 1, n, n
+        p.tokens = torch.empty(n, ac.ncam, NPATCH, ac.dino_dim, device=dev, dtype=ac.adt)
+        for cam in range(ac.ncam):                               # only the model's cameras are read
+            ops.feat_to_tokens(self._features(obs, cam).reshape(n, ac.dino_dim, NPATCH).contiguous(), p.tokens, cam, ncam=ac.ncam)
+        p.time_step, p.prev_actions, p.masks = rows[3].long(), rows[4].long(), (rows[3] > 0).to(F32)
+        p.hand = rows[5].long() if ac.has_hand else None
+        p.traj_bt = rows[0].reshape(n, 1)                        # (one episode per row; the per-row step does not read it)
+        p.ids, p.attn_mask, p.attn_mask_u8 = ids, am, am_u8
+        p.U, p.L, p.S = self.num_episodes, L, ac.text_off + L
+        p.ids_key = key                                          # eval mode: the frozen text encoder reruns only when a goal changed
+        p.gid = rows[0]                                          # row -> its slot's goal
+        p.row_cache, p.row_pos, p.row_klen = rows[0], rows[1], rows[2]
+        if kvalid is not None and any(lens[s] < L for s in slots):
+            p.fusion_kvalid = kvalid.index_select(0, rows[0].long())
+        version = ac._kv_version
+        ac._ensure_caches(self.num_episodes)
+        if ac._kv_version != version:
+            # the actor tower's caches were replaced.  Recorded acting plans are keyed by the cache version and recorded plans assert it, so none would be replayed
+            # on the old caches -- but they (and the engine's recorded env-chunks, through the hooks) would keep the old caches alive and point into them: drop them
+            # here, outside any recording (inside ``_ensure_caches`` the call would clear the plan table under a recording ``static_step``)
+            ac.invalidate_recorded()
+        logits, _, _ = ac.run_forward(p, need_grad=False)        # the actor tower (= the policy itself) alone
+        _, probs, sampled, greedy = ops.policy_sample_rows(logits.view(n, -1), rows[0], rows[3], self.seed)
+        picks = torch.stack([sampled, greedy]).tolist()          # the call's one host read
+        names, out = self.get_action_list(), {}
+        for j, s in enumerate(slots):
+            self._last[s], self._age[s] = picks[0][j], self._age[s] + 1
+            out[s] = (names[picks[1 if self.greedy_sampling else 0][j]], probs[j])
+        return out

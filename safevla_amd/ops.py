@@ -773,6 +773,26 @@ def ce_loss_fwd_bwd(logits, target, n_valid, dlogits, sums, ignore_index=-1):
     lib().call("svla_ce_loss_fwd_bwd_f32", _p(logits), _p(target), rows, A, int(ignore_index), _p(n_valid), _p(dlogits), _p(sums), _stream())
 
 
+def policy_sample_rows(logits, slot, age, seed, ld=None, out=None):
+    """The policy read-out of an acting step in one launch (csrc/sample.hip; the contract is in include/svla.h): logits [n, A <= 64] fp32 with rows ``ld`` apart
+    (default: the tensor's row stride), slot / age int32 [n] device tensors, ``seed`` an integer (its low 32 bits) -> (log_probs [n, A], probs [n, A], sampled [n],
+    greedy [n]); the last two int32.  The draw of row r is a function of (seed, slot[r], age[r]) alone.  ``out``: the four tensors to write into."""
+    _chk(logits, F32, "logits")
+    _chk(slot, torch.int32, "slot")
+    _chk(age, torch.int32, "age")
+    n, A = logits.shape
+    if logits.stride(-1) != 1 or min(slot.numel(), age.numel()) < n:
+        raise ValueError("policy_sample_rows: logits rows must be dense, slot and age hold one entry per row")
+    ld = logits.stride(0) if ld is None else ld
+    if out is None:
+        out = (torch.empty(n, A, device=logits.device, dtype=F32), torch.empty(n, A, device=logits.device, dtype=F32),
+               torch.empty(n, device=logits.device, dtype=torch.int32), torch.empty(n, device=logits.device, dtype=torch.int32))
+    seed = int(seed) & 0xFFFFFFFF
+    lib().call("svla_policy_sample_rows_f32", _p(logits), int(ld), _p(slot), _p(age), seed - (1 << 32) if seed >> 31 else seed, int(n), int(A), _p(out[0]), _p(out[1]),
+               _p(out[2]), _p(out[3]), _stream())
+    return out
+
+
 def cast_bf16(src, dst):
     if dst.dtype == F32:          # fp32 verification mode: activations stay fp32
         dst.copy_(src)
