@@ -23,6 +23,7 @@ from . import checkpoint
 from .preproc import DinoViTPreprocessor
 from .storage import RolloutStorage
 from .text import str_to_bytes
+from .vector_slots import EpisodeSlots, goal_ids, restart_slot
 
 # Stretch action vocabulary in the order of the policy head (utils/constants/stretch_initialization_utils.py:145-166,
 # short names utils/type_utils.py:55-74; the ACTION_DICT / LONG_ACTION_NAME environment overrides are honoured like upstream)
@@ -35,6 +36,17 @@ STRETCH_LONG_NAMES = {"m": "move_ahead", "r": "rotate_right", "l": "rotate_left"
                       "yps": "move_arm_up_small", "d": "dropoff"}
 # what a navigation-only policy may choose (dinov2_vits_tsfm_base.py:272-289): move_ahead, rotate_right, rotate_left, move_back, done, rotate_right_small, rotate_left_small
 NAV_ACTIONS = ("m", "r", "l", "b", "end", "rs", "ls")
+
+
+def camera_preprocessors(uuids, device, nav_pre=None, manip_pre=None):
+    """-> (nav_pre, manip_pre): the frozen ViT fronts of the two cameras' raw frames, built where none was passed in.  One frozen ViT serves both cameras only when
+    neither was passed in; a policy without the manipulation camera (manipulation_rgb_dino_preprocessor_uuid=None) gets no preprocessor for it"""
+    shared = nav_pre is None and manip_pre is None
+    nav_pre = nav_pre or DinoViTPreprocessor("rgb_raw", uuids["nav"], device=device)
+    manip_pre = None if uuids["manip"] is None else (manip_pre or DinoViTPreprocessor("manipulation_rgb_raw", uuids["manip"], device=device))
+    if shared and manip_pre is not None:
+        manip_pre.vit = nav_pre.vit
+    return nav_pre, manip_pre
 
 
 class AbstractAgent:
@@ -57,11 +69,7 @@ class InferenceAgentVIDA(AbstractAgent):
         self.device = torch.device(device)
         self.greedy_sampling = greedy_sampling
         u = actor_critic.uuids
-        self.nav_pre = nav_preprocessor or DinoViTPreprocessor("rgb_raw", u["nav"], device=device)
-        # a policy without the manipulation camera (manipulation_rgb_dino_preprocessor_uuid=None) gets no preprocessor for it
-        self.manip_pre = None if u["manip"] is None else (manip_preprocessor or DinoViTPreprocessor("manipulation_rgb_raw", u["manip"], device=device))
-        if self.manip_pre is not None and manip_preprocessor is None and nav_preprocessor is None:
-            self.manip_pre.vit = self.nav_pre.vit            # one frozen ViT serves both cameras
+        self.nav_pre, self.manip_pre = camera_preprocessors(u, device, nav_preprocessor, manip_preprocessor)
         self.steps_before_rollout_refresh = steps_before_rollout_refresh
         self.rollout_storage = RolloutStorage(steps_before_rollout_refresh, device=device, store_tokens=True,
                                               nav_uuid=u["nav"], manip_uuid=u["manip"])
@@ -257,18 +265,13 @@ class VectorInferenceAgentVIDA:
 
     def __init__(self, actor_critic, num_episodes: int, device="cuda", greedy_sampling: bool = False, nav_preprocessor=None, manip_preprocessor=None, seed: int = 0):
         from .model import BF16
-        if not 1 <= int(num_episodes) <= 1024:
-            raise ValueError(f"num_episodes = {num_episodes}: 1 ... 1024 episodes per vector agent")
+        self._slots = EpisodeSlots(num_episodes, 0)            # last action: the action sampled at the slot's last step
         if actor_critic.adt != BF16:
             raise NotImplementedError("precision='fp32': the acting step on per-row KV rings exists on the bf16 product path only")
         self.actor_critic, self.device, self.greedy_sampling = actor_critic, torch.device(device), greedy_sampling
-        self.num_episodes, self.seed = int(num_episodes), int(seed)
+        self.num_episodes, self.seed = self._slots.num_episodes, int(seed)
         self.window = actor_critic.max_steps
         self.nav_pre, self.manip_pre = nav_preprocessor, manip_preprocessor
-        self._age = [None] * self.num_episodes                 # host-side: steps taken in the slot's episode (None: not started)
-        self._last = [0] * self.num_episodes                   # the action sampled at the slot's last step
-        self._goal_ids = [None] * self.num_episodes            # token ids without padding, as tuples
-        self._goals = None                                     # _goal_table() of the current goals; None: a goal changed
         self._warned_window = False
         actor_critic.eval()
 
@@ -276,62 +279,19 @@ class VectorInferenceAgentVIDA:
 
     def _preprocessors(self):
         """the frozen ViT front of raw frames, built on first use (pre-encoded features never need it); one ViT serves both cameras, as in ``InferenceAgentVIDA``"""
-        u = self.actor_critic.uuids
-        shared = self.nav_pre is None and self.manip_pre is None
-        if self.nav_pre is None:
-            self.nav_pre = DinoViTPreprocessor(self._PRE_INPUTS[0], u["nav"], device=self.device)
-        if self.manip_pre is None and u["manip"] is not None:
-            self.manip_pre = DinoViTPreprocessor(self._PRE_INPUTS[1], u["manip"], device=self.device)
-            if shared:
-                self.manip_pre.vit = self.nav_pre.vit
+        self.nav_pre, self.manip_pre = camera_preprocessors(self.actor_critic.uuids, self.device, self.nav_pre, self.manip_pre)
 
     def age(self, slot: int) -> int:
-        return self._age[self._started(slot)]
-
-    def _slot(self, slot) -> int:
-        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.num_episodes:
-            raise KeyError(slot)
-        return int(slot)
-
-    def _started(self, slot) -> int:
-        slot = self._slot(slot)
-        if self._age[slot] is None:
-            raise KeyError(slot)
-        return slot
+        return self._slots.age(slot)
 
     def reset(self, slot: int, goal_spec):
         """Start an episode in ``slot``.  ``goal_spec``: a string (tokenised here, once, with ``actor_critic.tokenizer``) or token ids -- ``{"input_ids"[,
         "attention_mask"]}`` or an id sequence; right-padded ids keep their tokens"""
-        slot = self._slot(slot)
-        if isinstance(goal_spec, str):
-            ids = self.actor_critic.tokenizer.encode(goal_spec)
-        elif isinstance(goal_spec, dict):
-            ids = torch.as_tensor(goal_spec["input_ids"]).reshape(-1)
-            if "attention_mask" in goal_spec:
-                ids = ids[: int(torch.as_tensor(goal_spec["attention_mask"]).sum())]
-            ids = ids.tolist()
-        else:
-            ids = torch.as_tensor(goal_spec).reshape(-1).tolist()
-        ids = tuple(int(v) for v in ids)
-        if not ids:
+        slot = self._slots.slot(slot)
+        ids = goal_ids(self.actor_critic.tokenizer.encode(goal_spec) if isinstance(goal_spec, str) else goal_spec)
+        if not ids:                                              # this agent only: the IL vector agent takes an empty goal as it comes
             raise ValueError("an empty goal")
-        if ids != self._goal_ids[slot]:
-            self._goal_ids[slot], self._goals = ids, None
-        self._age[slot], self._last[slot] = 0, 0
-
-    def _goal_table(self):
-        """-> (ids_key, ids [N, L] of all slots (row = slot, right-padded to the longest; a slot that never started holds one end-of-sequence token), the T5 padding
-        mask [N, L] as int64 and uint8, fusion key mask [N, S] uint8 or None without padding, goal length per slot, L); rebuilt when a goal changed"""
-        if self._goals is None:
-            dev, off = self.device, self.actor_critic.text_off
-            rows = [g if g is not None else (1,) for g in self._goal_ids]
-            lens = [len(g) for g in rows]
-            L = max(lens)
-            ids = torch.tensor([list(g) + [0] * (L - len(g)) for g in rows], dtype=torch.int64)
-            mask = torch.arange(L)[None, :] < torch.tensor(lens)[:, None]
-            kvalid = torch.cat([torch.ones(len(rows), off, dtype=torch.uint8), mask.to(torch.uint8)], 1).contiguous().to(dev) if min(lens) < L else None
-            self._goals = (("vector", tuple(rows)), ids.to(dev), mask.to(torch.int64).to(dev), mask.to(torch.uint8).to(dev), kvalid, lens, L)
-        return self._goals
+        self._slots.start(slot, ids)
 
     def _features(self, obs, cam: int) -> torch.Tensor:
         """camera ``cam`` of the call's frames -> features [n, 384, 7, 12] fp32: pre-encoded ones as they come, raw uint8 frames through ONE batched pass of the ViT"""
@@ -350,19 +310,19 @@ class VectorInferenceAgentVIDA:
     def get_actions(self, frames: Dict[int, Dict[str, Any]]) -> Dict[int, Tuple[str, torch.Tensor]]:
         from . import ops
         from .model import F32, NPATCH, Prep
-        ac, dev = self.actor_critic, self.device
+        ac, dev, sl = self.actor_critic, self.device, self._slots
         if not frames:
             raise ValueError("get_actions needs the frames of at least one started slot")
-        slots = [self._started(s) for s in frames]
+        slots, ages, last = sl.rows(frames)
         obs, n, W = list(frames.values()), len(frames), self.window
-        ages = [self._age[s] for s in slots]
         if not self._warned_window and any(a and a % W == 0 for a in ages):
             warnings.warn(f"episode longer than the {W}-step KV-cache window (max_steps): the window restarts, as the reference's step counter does")
             self._warned_window = True
-        key, ids, am, am_u8, kvalid, lens, L = self._goal_table()
+        t = sl.goal_table(dev, ac.text_off)
+        pos, klen = zip(*(restart_slot(a, W) for a in ages))
         hand = [int(np.asarray(o.get("an_object_is_in_hand", 0)).reshape(-1)[0]) for o in obs] if ac.has_hand else [0] * n
         # the step's one small upload, per row: cache row (= slot), ring slot to write, slots to read, age, previous action, in-hand sensor
-        rows = torch.tensor([slots, [a % W for a in ages], [a % W + 1 for a in ages], ages, [self._last[s] for s in slots], hand], dtype=torch.int32).to(dev)
+        rows = torch.tensor([slots, pos, klen, ages, last, hand], dtype=torch.int32).to(dev)
         p = Prep()
         p.T, p.B, p.R = 1, n, n
         p.tokens = torch.empty(n, ac.ncam, NPATCH, ac.dino_dim, device=dev, dtype=ac.adt)
@@ -371,13 +331,13 @@ class VectorInferenceAgentVIDA:
         p.time_step, p.prev_actions, p.masks = rows[3].long(), rows[4].long(), (rows[3] > 0).to(F32)
         p.hand = rows[5].long() if ac.has_hand else None
         p.traj_bt = rows[0].reshape(n, 1)                        # (one episode per row; the per-row step does not read it)
-        p.ids, p.attn_mask, p.attn_mask_u8 = ids, am, am_u8
-        p.U, p.L, p.S = self.num_episodes, L, ac.text_off + L
-        p.ids_key = key                                          # eval mode: the frozen text encoder reruns only when a goal changed
+        p.ids, p.attn_mask, p.attn_mask_u8 = t.ids, t.mask, t.mask_u8
+        p.U, p.L, p.S = self.num_episodes, t.L, ac.text_off + t.L
+        p.ids_key = t.key                                        # eval mode: the frozen text encoder reruns only when a goal changed
         p.gid = rows[0]                                          # row -> its slot's goal
         p.row_cache, p.row_pos, p.row_klen = rows[0], rows[1], rows[2]
-        if kvalid is not None and any(lens[s] < L for s in slots):
-            p.fusion_kvalid = kvalid.index_select(0, rows[0].long())
+        if t.kvalid is not None and any(t.lens[s] < t.L for s in slots):
+            p.fusion_kvalid = t.kvalid.index_select(0, rows[0].long())
         version = ac._kv_version
         ac._ensure_caches(self.num_episodes)
         if ac._kv_version != version:
@@ -390,6 +350,6 @@ class VectorInferenceAgentVIDA:
         picks = torch.stack([sampled, greedy]).tolist()          # the call's one host read
         names, out = self.get_action_list(), {}
         for j, s in enumerate(slots):
-            self._last[s], self._age[s] = picks[0][j], self._age[s] + 1
+            sl.advance(s, picks[0][j])
             out[s] = (names[picks[1 if self.greedy_sampling else 0][j]], probs[j])
         return out

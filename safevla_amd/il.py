@@ -21,6 +21,7 @@ import torch
 
 from . import ops
 from .model import BF16, CAMERAS, DINO, F32, N_ACTIONS, NPATCH, Prep, Tower, _Arena, _TowerFn, sensor_set
+from .vector_slots import EpisodeSlots, goal_ids, ring_slot      # (ring_slot stays importable from here)
 
 NAV, MANIP = CAMERAS
 START_TOKEN, PAD_TOKEN = N_ACTIONS, N_ACTIONS + 1      # last_actions vocabulary (:95-101)
@@ -329,10 +330,8 @@ class EarlyFusionCnnTransformerAgent:
     def get_action(self, observations: Dict, goal_spec):
         m, dev = self.model, self.device
         if self.curr_t == 0:
-            self.cache["goal"] = self._goal(goal_spec)
-            g = self.cache["goal"]
-            ids = g["input_ids"] if isinstance(g, dict) else g
-            self.cache["goal_key"] = tuple(int(v) for v in ids.reshape(-1).tolist())
+            g = self.cache["goal"] = self._goal(goal_spec)
+            self.cache["goal_key"] = goal_ids(g["input_ids"] if isinstance(g, dict) else g)      # (every id, padding included: the key the text features are cached under)
         slot = self.curr_t % self.max_seq_len
         if slot == 0:
             m.time_step_counter = 0
@@ -365,14 +364,6 @@ class EarlyFusionCnnTransformerAgent:
         return self.action_list[idx], probs
 
 
-def ring_slot(age: int, window: int):
-    """Step ``age`` of an episode on a KV ring of ``window`` slots -> (slot the step is written to, number of slots its query reads).  The llama decoder applies
-    no RoPE and the time encoding is added to the input, so a single query does not care in which order its keys lie: slots [0, klen) ARE the last
-    min(age + 1, window) steps.  The same slot holds the step's decoder input in the history ring that the sliding window of
-    early_fusion_tsfm_models.py:491-497 is decoded from once the episode is older than the window."""
-    return age % window, min(age + 1, window)
-
-
 class EarlyFusionCnnTransformerVectorAgent:
     """``num_episodes`` online episodes of the imitation-learning model behind one set of weights: what ``EarlyFusionCnnTransformerAgent`` does for one episode
     (early_fusion_tsfm_models.py:366-520), for a vector of them that start, end and stall independently -- the evaluation workers of the reference hold one model
@@ -389,85 +380,38 @@ class EarlyFusionCnnTransformerVectorAgent:
 
     The slots' cache rows are the model's: a single agent on the same model writes cache row 0, so run one kind of agent on a model at a time."""
 
-    _setup, _goal = EarlyFusionCnnTransformerAgent._setup, EarlyFusionCnnTransformerAgent._goal
+    _setup, _goal, get_action_list = EarlyFusionCnnTransformerAgent._setup, EarlyFusionCnnTransformerAgent._goal, EarlyFusionCnnTransformerAgent.get_action_list
 
     def __init__(self, model: EarlyFusionCnnTransformer, num_episodes: int, device="cuda", sampling: str = "greedy", max_seq_len: int = 1000, tokenizer=None,
                  generator: Optional[torch.Generator] = None):
-        if not 1 <= int(num_episodes) <= 1024:
-            raise ValueError(f"num_episodes = {num_episodes}: 1 ... 1024 episodes per vector agent")
+        self._slots = EpisodeSlots(num_episodes, START_TOKEN)
         self._setup(model, device, sampling, max_seq_len, tokenizer, generator)
-        self.num_episodes = int(num_episodes)
-        self._age = [None] * self.num_episodes                 # host-side: steps taken in the slot's episode (None: not started)
-        self._last = [START_TOKEN] * self.num_episodes
-        self._goal_ids = [None] * self.num_episodes            # token ids without padding, as tuples
-        self._goals = None                                     # _goal_table() of the current goals; None: a goal changed
-
-    def get_action_list(self):
-        return self.action_list
+        self.num_episodes = self._slots.num_episodes
 
     def age(self, slot: int) -> int:
-        return self._age[self._started(slot)]
-
-    def _slot(self, slot) -> int:
-        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)) or not 0 <= slot < self.num_episodes:
-            raise KeyError(slot)
-        return int(slot)
-
-    def _started(self, slot) -> int:
-        slot = self._slot(slot)
-        if self._age[slot] is None:
-            raise KeyError(slot)
-        return slot
+        return self._slots.age(slot)
 
     def reset(self, slot: int, goal_spec):
-        slot = self._slot(slot)
-        g = self._goal(goal_spec)
-        if isinstance(g, dict):
-            ids = g["input_ids"].reshape(-1)
-            if "attention_mask" in g:                          # right-padded ids: keep the tokens
-                ids = ids[: int(g["attention_mask"].sum())]
-        else:
-            ids = g.reshape(-1)
-        ids = tuple(int(v) for v in ids.tolist())
-        if ids != self._goal_ids[slot]:
-            self._goal_ids[slot], self._goals = ids, None
-        self._age[slot], self._last[slot] = 0, START_TOKEN
-
-    def _goal_table(self):
-        """-> (ids_key, all slots' goals as the ``goals`` of ``prepare`` (row = slot, right-padded to the longest, length L; a slot that never started holds one
-        end-of-sequence token), fusion key mask [N, S] uint8 or None without padding, goal length per slot, L); rebuilt when a goal changed"""
-        if self._goals is None:
-            m, dev = self.model, self.device
-            rows = [g if g is not None else (1,) for g in self._goal_ids]
-            lens = [len(g) for g in rows]
-            L = max(lens)
-            ids = torch.tensor([list(g) + [0] * (L - len(g)) for g in rows], dtype=torch.int64)
-            if m.text_encoder_name == "t5-small":
-                mask = (torch.arange(L)[None, :] < torch.tensor(lens)[:, None])
-                goals = dict(input_ids=ids.to(dev), attention_mask=mask.to(torch.int64).to(dev))
-                kvalid = torch.cat([torch.ones(len(rows), m.text_off, dtype=torch.uint8), mask.to(torch.uint8)], 1).contiguous().to(dev) if min(lens) < L else None
-            else:                                              # SigLIP: a fixed context, nothing to hide (slots that never started: pad ids up to it)
-                goals, kvalid, lens = ids.to(dev), None, [L] * len(rows)
-            self._goals = (("vector", tuple(rows)), goals, kvalid, lens, L)
-        return self._goals
+        slot = self._slots.slot(slot)
+        self._slots.start(slot, goal_ids(self._goal(goal_spec) if isinstance(goal_spec, str) else goal_spec))
 
     @torch.no_grad()
     def get_actions(self, observations: Dict[int, Dict]) -> Dict[int, tuple]:
-        m, dev = self.model, self.device
+        m, dev, sl = self.model, self.device, self._slots
         if not observations:
             raise ValueError("get_actions needs the observations of at least one started slot")
         n, W = len(observations), self.max_seq_len
         # episodes that have outlived their window go last: the model decodes them over the window instead of against the KV ring (stable: the order stays otherwise)
-        order = sorted(((self._started(s), o) for s, o in observations.items()), key=lambda so: self._age[so[0]] >= W)
-        slots, obs = [s for s, _ in order], [o for _, o in order]
-        key, goals, kvalid, lens, L = self._goal_table()
-        ring = [ring_slot(self._age[s], W) for s in slots]
+        order = sorted(zip(*sl.rows(observations), observations.values()), key=lambda r: r[1] >= W)
+        slots, ages, last, obs = zip(*order)
+        t = sl.goal_table(dev, m.text_off, padded=m.text_encoder_name == "t5-small")
+        pos, klen = zip(*(ring_slot(a, W) for a in ages))
         # the step's one small upload: cache row (= slot), ring slot to write, slots to read, per row
-        rows = torch.tensor([slots, [p for p, _ in ring], [k for _, k in ring]], dtype=torch.int32).to(dev)
+        rows = torch.tensor([slots, pos, klen], dtype=torch.int32).to(dev)
         col = lambda v, dt: torch.as_tensor(np.asarray(v)).to(dt).reshape(n, 1)
-        batch = {"goals": goals, "time_ids": col([self._age[s] for s in slots], torch.int64)}      # the episode's age, as early_fusion_tsfm_models.py:480
+        batch = {"goals": dict(input_ids=t.ids, attention_mask=t.mask), "time_ids": col(ages, torch.int64)}      # the episode's age, as early_fusion_tsfm_models.py:480
         if m.has_prev:
-            batch["last_actions"] = col([self._last[s] for s in slots], torch.int64)
+            batch["last_actions"] = col(last, torch.int64)
         if m.has_hand:
             batch["an_object_is_in_hand"] = col([np.asarray(o.get("an_object_is_in_hand", 0)).reshape(-1)[0] for o in obs], torch.int64)
         for cam in m.cameras:
@@ -478,12 +422,12 @@ class EarlyFusionCnnTransformerVectorAgent:
             batch[cam] = x.reshape((n, 1) + tuple(x.shape[1:]))
         prep = m.prepare(batch)
         prep.acting = True
-        prep.ids_key = key                                     # eval mode: the frozen text encoder reruns only when a goal changed
+        prep.ids_key = t.key                                   # eval mode: the frozen text encoder reruns only when a goal changed
         prep.gid = rows[0]                                     # row -> its slot's goal
         prep.row_cache, prep.row_pos, prep.row_klen = rows[0], rows[1], rows[2]
-        prep.row_window, prep.row_slide = W, sum(self._age[s] >= W for s in slots)
-        if kvalid is not None and any(lens[s] < L for s in slots):
-            prep.fusion_kvalid = kvalid.index_select(0, rows[0])
+        prep.row_window, prep.row_slide = W, sum(a >= W for a in ages)
+        if t.kvalid is not None and any(t.lens[s] < t.L for s in slots):
+            prep.fusion_kvalid = t.kvalid.index_select(0, rows[0])
         m._ensure_caches(self.num_episodes)
         m._ensure_history(self.num_episodes, W)
         logits, _, _ = m.run_forward(prep, need_grad=False)
@@ -491,6 +435,6 @@ class EarlyFusionCnnTransformerVectorAgent:
         idx = torch.argmax(probs, -1) if self.sampling == "greedy" else torch.multinomial(probs, 1, generator=self.generator).reshape(-1)
         out = {}
         for j, (s, i) in enumerate(zip(slots, idx.tolist())):  # the call's one host read
-            self._last[s], self._age[s] = i, self._age[s] + 1
+            sl.advance(s, i)
             out[s] = (self.action_list[i], probs[j])
         return out

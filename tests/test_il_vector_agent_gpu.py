@@ -3,10 +3,16 @@
 
 Reference of every check: ``forward(batch)`` of the same model on ONE episode alone (B = 1, its goal unpadded, ``last_actions`` = the agent's own actions shifted,
 start token first) -- the comparison of tests/test_il_gpu.py::test_il_agent_steps_equal_full_sequence_forward, and its gate: 2e-2 * max(ref.max(), 1e-3) on the
-action probabilities of every step."""
+action probabilities of every step (tests/helpers/vector_agents.py)."""
+import os
+import sys
+
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers.vector_agents import Episode as _Episode, gate as _gate, staggered_episodes      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -61,22 +67,6 @@ def _forward_probs(m, frames, goal, time_ids, last_actions):
         return torch.softmax(m(batch)["actions_logits"][0].float(), -1).cpu().numpy()
 
 
-def _gate(got, ref, name):
-    err, tol = np.abs(got - ref).max(), 2e-2 * max(ref.max(), 1e-3)
-    print(f"{name}: max |dp| {err:.3e}, gate {tol:.3e}")
-    assert err < tol, (name, err, tol)
-
-
-class _Episode:
-    def __init__(self, goal):
-        self.goal, self.frames, self.acts, self.probs = goal, [], [], []
-
-    def record(self, agent, frame, out):
-        a, p = out
-        assert p.shape == (20,) and abs(float(p.sum()) - 1.0) < 1e-4
-        self.frames.append(frame); self.acts.append(agent.get_action_list().index(a)); self.probs.append(p.float().cpu().numpy())
-
-
 @pytest.mark.parametrize("version", VERSIONS)
 def test_staggered_episodes_equal_their_own_forward(version):
     """Three slots with goals of 3, 5 and 7 tokens that start at calls 0, 2 and 4; slot 1 sits out calls 5 and 6; slot 0 is reset after 5 steps with a goal of
@@ -84,30 +74,8 @@ def test_staggered_episodes_equal_their_own_forward(version):
     another slot's step, a stalled slot does not age."""
     m = _model(version)
     rs = np.random.RandomState(8)
-    agent = _vector_agent(m, 3)
-    assert agent.num_episodes == 3 and len(agent.get_action_list()) == 20
-    start = {0: 0, 1: 2, 2: 4}
-    lengths = {0: 3, 1: 5, 2: 7}
-    live, done = {}, []
-    for call in range(12):
-        for s, c0 in start.items():
-            if call == c0:
-                live[s] = _Episode(_goal(m, rs, lengths[s]))
-                agent.reset(s, live[s].goal)
-        if call == 5:                                                       # slot 0 has taken 5 steps: a new episode with a goal of another length
-            assert agent.age(0) == 5
-            done.append(live[0])
-            live[0] = _Episode(_goal(m, rs, 4))
-            agent.reset(0, live[0].goal)
-        active = [s for s in sorted(live) if not (s == 1 and call in (5, 6))]
-        frames = {s: _frame(m, rs) for s in active}
-        out = agent.get_actions(frames)
-        assert sorted(out) == active
-        for s in active:
-            live[s].record(agent, frames[s], out[s])
-    assert [agent.age(s) for s in range(3)] == [7, 8, 8]                    # slot 1 did not age while it sat out
-    done += [live[s] for s in sorted(live)]
-    assert [len(e.acts) for e in done] == [5, 7, 8, 8]
+    lengths = {0: 3, 1: 5, 2: 7, "reset": 4}
+    done = staggered_episodes(_vector_agent(m, 3), lambda s: _goal(m, rs, lengths[s]), lambda: _frame(m, rs))
     for i, e in enumerate(done):
         ref = _forward_probs(m, e.frames, e.goal, range(len(e.acts)), [20] + e.acts[:-1])
         _gate(np.stack(e.probs), ref, f"{version} episode {i} ({len(e.acts)} steps)")

@@ -5,11 +5,16 @@ Reference of every check: the same model's sequence forward on ONE episode alone
 no_grad in eval mode, a constant ``traj_index``, the goal unpadded, ``prev_actions`` = the agent's own sampled actions shifted by one, ``masks[0] = 0`` -- and the gate
 of tests/test_il_vector_agent_gpu.py: 2e-2 * max(ref.max(), 1e-3) on the action probabilities of every step.  (The forwards on steps 8 ... t of the window test do
 not start an episode: their first step has a previous action and ``masks`` = 1, as the agent and the reference's step counter have it at a cache restart.)"""
+import os
+import sys
 import warnings
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from helpers.vector_agents import Episode as _Episode, gate as _gate, staggered_episodes      # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -72,24 +77,9 @@ def _forward_probs(m, frames, goal, time_steps, prev_actions, first_mask=0.0):
     return out.distributions.probs[:, 0].float().cpu().numpy()
 
 
-def _gate(got, ref, name):
-    err, tol = np.abs(got - ref).max(), 2e-2 * max(ref.max(), 1e-3)
-    print(f"{name}: max |dp| {err:.3e}, gate {tol:.3e}")
-    assert err < tol, (name, err, tol)
-
-
-class _Episode:
-    def __init__(self, goal):
-        self.goal, self.frames, self.acts, self.probs = goal, [], [], []
-
-    def record(self, agent, frame, out):
-        a, p = out
-        assert p.shape == (20,) and abs(float(p.sum()) - 1.0) < 1e-4
-        self.frames.append(frame); self.acts.append(agent.get_action_list().index(a)); self.probs.append(p.float().cpu().numpy())
-
-    def check(self, m, name):
-        n = len(self.acts)
-        _gate(np.stack(self.probs), _forward_probs(m, self.frames, self.goal, range(n), [0] + self.acts[:-1]), f"{name} ({n} steps)")
+def _check(e, m, name):
+    n = len(e.acts)
+    _gate(np.stack(e.probs), _forward_probs(m, e.frames, e.goal, range(n), [0] + e.acts[:-1]), f"{name} ({n} steps)")
 
 
 @pytest.mark.parametrize("kind", ["full", "nav"])
@@ -99,33 +89,11 @@ def test_staggered_episodes_equal_their_own_forward(kind):
     another slot's step, a stalled slot does not age.  Once on the full sensor set, once with full_sensor=False (one camera, no in-hand sensor)."""
     m = _model(kind)
     rs = np.random.RandomState(8)
-    agent = _vector_agent(m, 3, seed=21)
-    assert agent.num_episodes == 3 and len(agent.get_action_list()) == 20
-    start = {0: 0, 1: 2, 2: 4}
     goals = {0: _goal(rs, 3), 1: "find a red mug", 2: _goal(rs, 7)}
     assert len(m.tokenizer.encode(goals[1])) == 5
-    live, done = {}, []
-    for call in range(12):
-        for s, c0 in start.items():
-            if call == c0:
-                live[s] = _Episode(goals[s])
-                agent.reset(s, live[s].goal)
-        if call == 5:                                                       # slot 0 has taken 5 steps: a new episode with a goal of another length
-            assert agent.age(0) == 5
-            done.append(live[0])
-            live[0] = _Episode(_goal(rs, 4))
-            agent.reset(0, live[0].goal)
-        active = [s for s in sorted(live) if not (s == 1 and call in (5, 6))]
-        frames = {s: _frame(rs) for s in active}
-        out = agent.get_actions(frames)
-        assert sorted(out) == active
-        for s in active:
-            live[s].record(agent, frames[s], out[s])
-    assert [agent.age(s) for s in range(3)] == [7, 8, 8]                    # slot 1 did not age while it sat out
-    done += [live[s] for s in sorted(live)]
-    assert [len(e.acts) for e in done] == [5, 7, 8, 8]
+    done = staggered_episodes(_vector_agent(m, 3, seed=21), lambda s: goals[s] if s in goals else _goal(rs, 4), lambda: _frame(rs))
     for i, e in enumerate(done):
-        e.check(m, f"{kind} episode {i}")
+        _check(e, m, f"{kind} episode {i}")
 
 
 def test_only_the_actor_tower_is_launched():
