@@ -826,7 +826,7 @@ def patchify_u8(frames_u8, mean3, std3, out, crop_x=3, P=14, gh=16, gw=27):
                (ctypes.c_float * 3)(*[float(v) for v in std3]), _p(out), _stream())
 
 
-# sampled frame augmentation (csrc/augment.hip): u8 [B,H,W,3] -> u8 [B,H,W,3] stages in front of normalize_u8 / patchify_u8
+# frame augmentation (csrc/augment.hip): u8 [B,H,W,3] -> u8 [B,H,W,3] stages in front of normalize_u8 / patchify_u8.  First the single-transform launches
 AUG_NPART = 64                                                  # integer partial sums per image (csrc/augment.hip: AUG_NPART)
 AUG_BRIGHTNESS, AUG_CONTRAST, AUG_SATURATION, AUG_HUE = 0, 1, 2, 3      # torchvision ColorJitter's operation codes
 
@@ -836,6 +836,14 @@ def _aug_frames(x_u8, name="frames"):
     if x_u8.dim() != 4 or x_u8.shape[-1] != 3 or not x_u8.is_contiguous():
         raise ValueError(f"{name}: expected a contiguous uint8 [B,H,W,3] tensor, got {tuple(x_u8.shape)}")
     return x_u8.shape[0], x_u8.shape[1], x_u8.shape[2]
+
+
+def _aug_out(x_u8, out):
+    """the output frames of an augmentation launch: ``out`` when given (checked like the input, same shape), else new frames shaped like the input"""
+    y = torch.empty_like(x_u8) if out is None else out
+    _aug_frames(y, "out")
+    assert y.shape == x_u8.shape
+    return y
 
 
 def _aug_ops(ops, factors):
@@ -859,9 +867,7 @@ def aug_jitter_blur(x_u8, ops=(), factors=(), partials=None, wx=None, wy=None, o
     blur -- one launch.  ``partials`` (aug_gray_partials of the frames entering contrast) is needed when contrast is among the operations."""
     B, H, W = _aug_frames(x_u8)
     n, packed, f = _aug_ops(ops, factors)
-    y = torch.empty_like(x_u8) if out is None else out
-    _aug_frames(y, "out")
-    assert y.shape == x_u8.shape
+    y = _aug_out(x_u8, out)
     cwx = (ctypes.c_float * 5)(*[float(v) for v in wx]) if wx is not None else None
     cwy = (ctypes.c_float * 9)(*[float(v) for v in wy]) if wy is not None else None
     lib().call("svla_aug_jitter_blur_u8", _p(x_u8), _p(y), B, H, W, n, packed, f[0], f[1], f[2], f[3], _p(partials), cwx, cwy, _stream())
@@ -873,14 +879,12 @@ def aug_resize_post_sharp(x_u8, box=None, posterize=False, sharpen=False, out=No
     sharpness factor 2 when ``sharpen`` -- one launch."""
     B, H, W = _aug_frames(x_u8)
     top, left, bh, bw = (0, 0, H, W) if box is None else [int(v) for v in box]
-    y = torch.empty_like(x_u8) if out is None else out
-    _aug_frames(y, "out")
-    assert y.shape == x_u8.shape
+    y = _aug_out(x_u8, out)
     lib().call("svla_aug_resize_post_sharp_u8", _p(x_u8), _p(y), B, H, W, top, left, bh, bw, int(bool(posterize)), int(bool(sharpen)), _stream())
     return y
 
 
-# per-trajectory random frame augmentation (csrc/augment_grouped.hip): the three launches above with one transform per group of frames
+# per-trajectory random frame augmentation (the grouped launches of csrc/augment.hip): the three launches above with one transform per group of frames
 class AugTransform(ctypes.Structure):
     """svla_aug_transform of include/svla.h: one entry of the table"""
     _fields_ = [("nops", ctypes.c_int), ("ops_packed", ctypes.c_int), ("f", ctypes.c_float * 4), ("nops_before_contrast", ctypes.c_int),
@@ -933,9 +937,7 @@ def aug_gray_partials_grouped(x_u8, table: AugTable, group_len):
 def aug_jitter_blur_grouped(x_u8, table: AugTable, group_len, partials, out=None):
     """aug_jitter_blur with one transform per group (ColorJitter in the group's order, then its 5 x 9 blur) -- one launch"""
     N, H, W, group_len = _aug_grouped_frames(x_u8, table, group_len)
-    y = torch.empty_like(x_u8) if out is None else out
-    _aug_frames(y, "out")
-    assert y.shape == x_u8.shape
+    y = _aug_out(x_u8, out)
     lib().call("svla_aug_jitter_blur_grouped_u8", _p(x_u8), _p(y), N, H, W, group_len, *table.args(), _p(partials), _stream())
     return y
 
@@ -943,9 +945,7 @@ def aug_jitter_blur_grouped(x_u8, table: AugTable, group_len, partials, out=None
 def aug_resize_post_sharp_grouped(x_u8, table: AugTable, group_len, out=None):
     """aug_resize_post_sharp with one transform per group (its crop box resized to the frame, x & its post_mask, its sharpness) -- one launch"""
     N, H, W, group_len = _aug_grouped_frames(x_u8, table, group_len)
-    y = torch.empty_like(x_u8) if out is None else out
-    _aug_frames(y, "out")
-    assert y.shape == x_u8.shape
+    y = _aug_out(x_u8, out)
     lib().call("svla_aug_resize_post_sharp_grouped_u8", _p(x_u8), _p(y), N, H, W, group_len, *table.args(), _stream())
     return y
 

@@ -1,4 +1,4 @@
-"""Per-trajectory random frame augmentation (csrc/augment_grouped.hip, preproc.apply_random_augment_u8): one transform per group of frames, three launches
+"""Per-trajectory random frame augmentation (the grouped kernels of csrc/augment.hip, preproc.apply_random_augment_u8): one transform per group of frames, three launches
 whatever the number of groups.
 
 The oracle is the single-transform path (preproc.apply_augment_u8), itself verified against its fp32 restatement in tests/test_augment_gpu.py: a grouped application

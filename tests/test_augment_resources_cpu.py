@@ -1,9 +1,13 @@
-"""Register / scratch / LDS figures of the frame-augmentation kernels (csrc/augment.hip), read from the compiled gfx950 code object (hipcc cross-compiles without a
-GPU; the mechanism of tests/test_attn_decode_resources_cpu.py).
+"""Register / scratch / LDS figures of the six frame-augmentation kernels (csrc/augment.hip), read from the compiled gfx950 code object (hipcc cross-compiles
+without a GPU; the mechanism of tests/helpers/kernel_resources.py).  The file is compiled once for both launch forms.
 
-The three kernels index no array dynamically (operation codes, factors and blur weights are scalar kernel arguments selected by unrolled code), so none may use
-scratch; their LDS is static: the staged chunk of the gray reduction, the jitter tile with its blur halo, the crop source rectangle plus the resized tile with its
-sharpness halo.  All three must keep at least four waves per SIMD (128 VGPRs): they are memory-bound streams that live on occupancy."""
+Single-transform kernels.  They index no array dynamically (operation codes, factors and blur weights are scalar kernel arguments selected by unrolled code), so
+none may use scratch; their LDS is static: the staged chunk of the gray reduction, the jitter tile with its blur halo, the crop source rectangle plus the resized
+tile with its sharpness halo.  All three must keep at least four waves per SIMD (128 VGPRs): they are memory-bound streams that live on occupancy.
+
+Grouped kernels.  They call the same three device bodies with their parameters read from a table entry instead of the kernel arguments.  A block serves one image,
+so the entry's address is uniform and the parameters must arrive as the kernel arguments do: in scalar registers.  Parameters that ended up in vector registers or
+scratch would show here as a higher VGPR count or a scratch size; the table is not staged in LDS, so the LDS sizes are exactly those of the single-transform kernels."""
 import os
 import sys
 
@@ -19,16 +23,41 @@ PINS = {
     "aug_resize_post_sharp_kernel": (32, 20 * ((128 + 4) * 3 + 12) + 18 * ((128 + 2) * 3 + 2) + 20),      # 25
 }
 
+# kernel -> (VGPRs exactly as measured when this was written, LDS bytes per block exactly: the figures of PINS)
+GROUPED_PINS = {
+    "aug_gray_partials_grouped_kernel": (38, 2048 * 3 + 16 + 4 * 8),                                              # 6 192 B; the single-transform kernel: 38 VGPRs
+    "aug_jitter_blur_grouped_kernel": (79, 24 * ((128 + 4) * 3 + 12) + 24 + 4),                                   # 9 820 B; 80 (the grouped form has no blur-off path)
+    "aug_resize_post_sharp_grouped_kernel": (25, 20 * ((128 + 4) * 3 + 12) + 18 * ((128 + 2) * 3 + 2) + 20),      # 15 236 B; 25
+}
 
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
-def test_augment_kernels_registers_scratch_and_lds():
+
+@pytest.fixture(scope="module")
+def res():
+    if not os.path.exists(HIPCC):
+        pytest.skip("needs hipcc")
     res = _resources("augment.hip")
-    assert len(res) == 3, sorted(res)
+    assert len(res) == 6, sorted(res)
+    return res
+
+
+def _kernel(res, name):
+    hits = [v for k, v in res.items() if name in k]
+    assert len(hits) == 1, (name, sorted(res))
+    v = hits[0]
+    print(name, v)
+    assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (name, v)
+    return v
+
+
+def test_augment_kernels_registers_scratch_and_lds(res):
     for name, (vgprs, lds) in PINS.items():
-        hits = [v for k, v in res.items() if name in k]
-        assert len(hits) == 1, (name, sorted(res))
-        v = hits[0]
-        print(name, v)
-        assert v["ScratchSize [bytes/lane]"] == 0 and v["VGPRs Spill"] == 0 and v["SGPRs Spill"] == 0, (name, v)
+        v = _kernel(res, name)
         assert v["VGPRs"] <= vgprs <= 128, (name, v)
+        assert v["LDS Size [bytes/block]"] == lds, (name, v, lds)
+
+
+def test_grouped_augment_kernels_registers_scratch_and_lds(res):
+    for name, (vgprs, lds) in GROUPED_PINS.items():
+        v = _kernel(res, name)
+        assert v["VGPRs"] == vgprs, (name, v)
         assert v["LDS Size [bytes/block]"] == lds, (name, v, lds)

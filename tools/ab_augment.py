@@ -6,7 +6,8 @@
     alternating the two within the run; the host draws of a call (ColorJitter order, crop box) are part of the step;
   * a hash of the un-augmented step's output tokens, to compare two trees on the same frames.
 
-Runs on a tree without the augmentation too (it then reports the plain step only): the same file times the parent commit.  Results: profiles/augment_ab.txt."""
+Runs on a tree without the augmentation too (it then reports the plain step only): the same file times the parent commit.  Results: profiles/augment_ab.txt;
+against the parent of the change that gave both launch forms one body per stage: profiles/augment_shared_ab.txt."""
 import argparse
 import hashlib
 import os

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Cost of the per-trajectory random frame augmentation (csrc/augment_grouped.hip) against the only route without it: one application of the single-transform
-launches (csrc/augment.hip) per trajectory, on that trajectory's slice of the batch.
+"""Cost of the per-trajectory random frame augmentation (the grouped kernels of csrc/augment.hip) against the only route without it: one application of the
+single-transform launches (same file, same device bodies) per trajectory, on that trajectory's slice of the batch.
 
   * leg A: G x preproc.apply_augment_u8 on the G slices (3 G launches, G host conversions); leg B: one preproc.apply_random_augment_u8 (3 launches, each with its
     108-byte-per-group table upload) -- at 16 trajectories x 8 frames of 224 x 384 (the camera) and of 256 x 256 (the SigLIP presets' input);
@@ -9,7 +9,7 @@ launches (csrc/augment.hip) per trajectory, on that trajectory's slice of the ba
 
 HIP events around `--reps` back-to-back applications after warm-up, the two legs alternated within one run, `--rounds` times; the host work of a leg (building the
 table, argument conversion) is inside its window.  Both legs write into preallocated outputs; their results are compared bit for bit before anything is timed.
-Results: profiles/augment_grouped_ab.txt."""
+Results: profiles/augment_grouped_ab.txt; against the parent of the change that gave both forms one body per stage: profiles/augment_shared_ab.txt."""
 import argparse
 import os
 import sys
