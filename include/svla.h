@@ -532,6 +532,26 @@ int svla_dropout_f32(float* x, long rows, int N, const svla_dropout* drop, void*
 int svla_policy_sample_rows_f32(const float* logits, long ld, const int* slot, const int* age, int seed, int n, int A, float* log_probs, float* probs,
                                 int* sampled, int* greedy, void* stream);
 
+/* ---- validation metrics of the imitation-learning trainer ---------------------------------------------------------------------------
+ * (Declared in front of the last section too: only svla_attn_causal_fwd_bf16 moves, by one.)
+ * What LitModel.validation_step does with the actor's logits (training/offline/train_pl.py:187-207,252-259: pred = argmax, three torchmetrics F1Score objects
+ * [3P, restated, unpinned: all three are functions of the confusion matrix], next to the nn.CrossEntropyLoss(ignore_index=-1) of
+ * early_fusion_tsfm_models.py:88,117-119) in one launch per batch (csrc/metrics.hip) and without a host read: counts and sums are ACCUMULATORS in device memory
+ * that the caller zeroes when an epoch starts; every launch adds to them.  logits [rows, ld] fp32, the first A columns of a row are read; target [rows] int64;
+ * counts [A, A] int64; sums [3] fp64; pred [rows] int32 or NULL.  For every row r with target[r] != ignore_index:
+ *   m = max_k logits[r, k] over k < A;   p = the lowest k with logits[r, k] == m  (the greedy rule of svla_policy_sample_rows_f32; torch.argmax on a row without NaN);
+ *   counts[target[r] * A + p] += 1;
+ *   sums[0] += (m + log(sum_k exp(logits[r, k] - m))) - logits[r, target[r]]   -- the row's term in fp32 with precise expf / logf, the sum over rows in fp64;
+ *   sums[1] += 1.
+ * A row whose target is neither ignore_index nor inside [0, A), or that holds a NaN among its A logits (and is not ignored), adds 1 to sums[2] and NOTHING else:
+ * counts is indexed with 0 <= target, p < A only, whatever the input.  A row with target[r] == ignore_index adds nothing to counts or sums.
+ * pred[r] = p for every row that has a maximum, ignored rows included; -1 for a row that holds a NaN.
+ * The counts are integers: exactly repeatable, and two launches on the halves of a batch leave what one launch on the whole leaves.  sums[0] is added with fp64
+ * atomics, one per workgroup: it may differ in its last bits with the order of the adds.
+ * SVLA_EINVAL, nothing launched: rows <= 0, A < 1 or A > 64, ld < A, a NULL logits, target, counts or sums. */
+int svla_action_metrics_f32(const float* logits, long ld, const long* target, int rows, int A, long ignore_index, long long* counts, double* sums, int* pred,
+                            void* stream);
+
 /* ---- causal attention over whole episodes ----------------------------------------------------------------------------------------
  * (Declared last: svla_replay_calls numbers the entry points in declaration order, and a new one must not move the others.)
  * The sequence form of the llama decoder's attention (llama/model.py:249-322 with the block-causal traj_index mask of early_fusion_tsfm_models.py:160-178, 491-497)

@@ -188,11 +188,16 @@ class EarlyFusionCnnTransformer(Tower):
         return DinoViTPreprocessor(key, key, dino_model_type={384: "dinov2_vits14", 768: "dinov2_vitb14", 1024: "dinov2_vitl14"}[self.dino_dim], device=dev)
 
     # ---- reference forward API --------------------------------------------------------------------------------------------------
-    def forward(self, batch: Dict) -> Dict[str, torch.Tensor]:
+    def _logits_tb(self, batch: Dict) -> torch.Tensor:
+        """The tower forward of a batch -> logits [T, B, A] fp32, rows in the kernels' order (t * B + b); shared by forward(batch) and ILTrainer.validation_step"""
         # whole episodes (512 < T <= 1000 steps) run forward only -- under torch.no_grad() or in eval mode; what cannot run is refused before the first launch
         self._check_seq_len(int(batch[self.cameras[0]].shape[1]), torch.is_grad_enabled() and self.training)
         prep = self.prepare(batch, augment=self.data_augmentation)
         logits, _, _ = _TowerFn.apply(self._anchor, self, prep, True, False)      # [T, B, A] fp32
+        return logits
+
+    def forward(self, batch: Dict) -> Dict[str, torch.Tensor]:
+        logits = self._logits_tb(batch)
         out = dict(actions_logits=logits.transpose(0, 1))
         if "actions" in batch:
             tgt = batch["actions"].to(self.device_).transpose(0, 1).reshape(-1).to(torch.int64)
@@ -239,12 +244,109 @@ class EarlyFusionCnnTransformer(Tower):
         return m
 
 
+def f1_from_counts(C) -> Dict:
+    """Per-class, macro and weighted F1 of a confusion matrix C[target, pred] (numpy or CPU torch, any integer dtype) -> dict(f1 = list of A, f1_macro, f1_weighted).
+
+    [3P] RESTATED, UNPINNED: this is how torchmetrics' multiclass ``F1Score`` (``average`` = None / "macro" / "weighted", top_k = 1, zero_division = 0; the three
+    objects of train_pl.py:200-207) reads, restated from its documentation -- torchmetrics is neither in the reference tree nor available offline, so nothing here
+    is compared against it.  With tp_k = C[k, k], fp_k = column sum - tp_k, fn_k = row sum - tp_k:
+      f1_k     = 2 tp_k / (2 tp_k + fp_k + fn_k), 0 where that denominator is 0;
+      macro    = mean of f1_k over the classes with tp_k + fp_k + fn_k > 0 (a class in neither targets nor predictions does not count);
+      weighted = sum_k (tp_k + fn_k) f1_k / sum_k (tp_k + fn_k)  (weights = the classes' support);
+    both 0.0, never NaN, when no class qualifies.  Rows with the ignored target never reach C.  Equal to sklearn.metrics.f1_score(labels=None) for the three averages
+    (tests/test_il_f1_cpu.py, where sklearn is installed)."""
+    C = np.asarray(C).astype(np.float64)
+    if C.ndim != 2 or C.shape[0] != C.shape[1]:
+        raise ValueError(f"f1_from_counts: a square confusion matrix, got {C.shape}")
+    tp = np.diag(C)
+    fp, fn = C.sum(0) - tp, C.sum(1) - tp
+    den = 2.0 * tp + fp + fn
+    f1 = np.divide(2.0 * tp, den, out=np.zeros_like(den), where=den > 0)
+    seen, support = den > 0, tp + fn
+    macro = float(f1[seen].mean()) if seen.any() else 0.0
+    weighted = float((support * f1).sum() / support.sum()) if support.sum() > 0 else 0.0
+    return dict(f1=[float(v) for v in f1], f1_macro=macro, f1_weighted=weighted)
+
+
+class ActionF1:
+    """The validation state of one epoch: the confusion matrix (target, greedy action) and the summed cross-entropy of every batch seen, kept where the logits are.
+    ``update`` is one launch of svla_action_metrics_f32 (csrc/metrics.hip) -- no host read, no allocation; ``reduce_`` sums the state over the ranks; ``compute`` is
+    the epoch's one host read.  The state is one int64 buffer: ``counts`` [A, A] views its first A * A words, ``sums`` [3] (loss sum, frames, refused rows) views the
+    last three as fp64.  On ``device="cpu"`` everything but ``update`` works (the reduction and the arithmetic are tested without a GPU)."""
+
+    def __init__(self, num_actions: int = N_ACTIONS, ignore_index: int = -1, device="cuda"):
+        if not 1 <= num_actions <= 64:
+            raise ValueError(f"num_actions = {num_actions}: svla_action_metrics_f32 takes 1 ... 64 actions")
+        self.num_actions, self.ignore_index = num_actions, ignore_index
+        self.state = torch.zeros(num_actions * num_actions + 3, device=device, dtype=torch.int64)
+        self.counts = self.state[:num_actions * num_actions].view(num_actions, num_actions)
+        self.sums = self.state[num_actions * num_actions:].view(torch.float64)
+
+    def update(self, logits_rows: torch.Tensor, target_rows: torch.Tensor):
+        """logits_rows [rows, A] fp32 (dense rows, any row stride), target_rows [rows] int64"""
+        ops.action_metrics(logits_rows, target_rows, self.counts, self.sums, self.ignore_index)
+
+    def reduce_(self):
+        """Every rank leaves with the sum of all ranks' states (a no-op on a single process)"""
+        from . import parallel
+        parallel.allreduce_sum_(self.counts)
+        parallel.allreduce_sum_(self.sums)
+
+    def compute(self) -> Dict:
+        """-> dict(f1, f1_macro, f1_weighted, loss, frames, confusion).  Raises if any row was refused: a diverged model (NaN logits) or a target outside
+        [0, A) must not report an F1."""
+        A = self.num_actions
+        host = self.state.cpu()                                  # the epoch's one host read
+        C, sums = host[:A * A].view(A, A).numpy(), host[A * A:].view(torch.float64).tolist()
+        if sums[2] > 0:
+            raise ValueError(f"validation refused {int(sums[2])} rows (NaN logits or a target outside [0, {A}) that is not ignore_index = {self.ignore_index}): no F1")
+        out = f1_from_counts(C)
+        out.update(loss=sums[0] / max(sums[1], 1.0), frames=int(sums[1]), confusion=C.copy())
+        return out
+
+    def reset(self):
+        self.state.zero_()
+
+
 class ILTrainer:
-    """``LitModel.training_step`` + ``configure_optimizers`` (training/offline/train_pl.py:154-186,283-287): AdamW(lr) on the flat arena."""
+    """``LitModel.training_step`` + ``configure_optimizers`` (training/offline/train_pl.py:154-186,283-287): AdamW(lr) on the flat arena; and its
+    ``validation_step`` / ``on_validation_epoch_end`` (:187-281) on the F1 state of ``ActionF1``."""
 
     def __init__(self, model: EarlyFusionCnnTransformer, lr: float = 1e-4, weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8):
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
         self.step_count = 0
+        self.val_metrics = ActionF1(N_ACTIONS, -1, device=model.device_)
+
+    def validation_step(self, batch: Dict) -> None:
+        """One held-out batch into the epoch's metrics (train_pl.py:187-207): the tower forward of ``forward(batch)`` in eval mode under ``torch.no_grad()`` (so windows of
+        513 ... 1024 steps validate), then ONE launch on the [T * B, A] logits: argmax, confusion counts and the summed cross-entropy (padded steps, actions = -1, add
+        nothing).  svla_ce_loss_fwd_bwd_f32 does not run; nothing is returned and nothing is read back.  The train / eval mode of the model is put back."""
+        m = self.model
+        was_training = m.training
+        m.eval()
+        try:
+            with torch.no_grad():
+                logits = m._logits_tb(batch)
+                tgt = batch["actions"].to(m.device_).transpose(0, 1).reshape(-1).to(torch.int64)      # rows (t * B + b), as forward(batch) orders them
+                self.val_metrics.update(logits.reshape(-1, N_ACTIONS), tgt)
+        finally:
+            m.train(was_training)
+
+    def validation_epoch_end(self) -> Dict[str, float]:
+        """The reference's log keys of a validation epoch (train_pl.py:252-281): f1score_weighted/val, f1score_macro/val, f1score/<action>/val for the 20 names of
+        ALL_STRETCH_ACTIONS, actions_loss/val and loss/val, plus val_frames (the non-padded steps seen, over all ranks).  Lightning logs the loss per step and averages
+        the steps' means; this is the epoch's mean over the valid steps instead.  Sums the state over the ranks, reads it once, and starts the next epoch at zero."""
+        from .agent import ALL_STRETCH_ACTIONS
+        vm = self.val_metrics
+        vm.reduce_()
+        try:
+            r = vm.compute()
+        finally:
+            vm.reset()
+        out = {"f1score_weighted/val": r["f1_weighted"], "f1score_macro/val": r["f1_macro"]}
+        out.update({f"f1score/{name}/val": v for name, v in zip(ALL_STRETCH_ACTIONS, r["f1"])})
+        out.update({"actions_loss/val": r["loss"], "loss/val": r["loss"], "val_frames": r["frames"]})
+        return out
 
     def training_step(self, batch: Dict) -> Dict[str, float]:
         m = self.model

@@ -793,6 +793,30 @@ def policy_sample_rows(logits, slot, age, seed, ld=None, out=None):
     return out
 
 
+def action_metrics(logits, target, counts, sums, ignore_index=-1, pred=None, ld=None):
+    """One validation batch into the epoch's accumulators in one launch (csrc/metrics.hip; the contract is in include/svla.h): logits [rows, A <= 64] fp32 with rows
+    ``ld`` apart (default: the tensor's row stride), target [rows] int64 -> counts [A, A] int64 += the confusion matrix (target, greedy action), sums [3] fp64 +=
+    (summed cross-entropy, rows counted, rows refused: target outside [0, A) or NaN logits); rows with target == ignore_index add nothing.  ``pred``: int32 [rows]
+    that receives the greedy action of every row (-1: a NaN row).  Nothing is read back and nothing is allocated."""
+    _chk(logits, F32, "logits")
+    _chk(target, torch.int64, "target")
+    _chk(counts, torch.int64, "counts")
+    _chk(sums, torch.float64, "sums")
+    if pred is not None:
+        _chk(pred, torch.int32, "pred")
+    if logits.dim() != 2:
+        raise ValueError(f"action_metrics: logits must be [rows, A], got {tuple(logits.shape)}")
+    rows, A = logits.shape
+    if any(t is not None and t.device != logits.device for t in (target, counts, sums, pred)):
+        raise ValueError("action_metrics: logits, target, counts, sums and pred must live on one device")
+    if logits.stride(-1) != 1 or target.numel() != rows or not target.is_contiguous() or (pred is not None and (pred.numel() != rows or not pred.is_contiguous())):
+        raise ValueError("action_metrics: logits rows must be dense, target (and pred) hold one contiguous entry per row")
+    if tuple(counts.shape) != (A, A) or not counts.is_contiguous() or sums.numel() != 3 or not sums.is_contiguous():
+        raise ValueError(f"action_metrics: counts must be a contiguous [{A}, {A}] and sums hold 3 values, got {tuple(counts.shape)} and {tuple(sums.shape)}")
+    ld = (logits.stride(0) if rows > 1 else A) if ld is None else ld
+    lib().call("svla_action_metrics_f32", _p(logits), int(ld), _p(target), int(rows), int(A), int(ignore_index), _p(counts), _p(sums), _p(pred), _stream())
+
+
 def cast_bf16(src, dst):
     if dst.dtype == F32:          # fp32 verification mode: activations stay fp32
         dst.copy_(src)

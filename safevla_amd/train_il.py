@@ -65,6 +65,10 @@ def main():
                     help="with --raw_frames: the random v2 frame augmentation, one newly drawn transform per trajectory and camera (the reference trains with it on "
                          "unless --no_augmentation, train_pl.py:92; off here unless asked for)")
     ap.add_argument("--init_ckpt", default=None)
+    ap.add_argument("--eval_every", type=int, default=0,
+                    help="validate every N steps on held-out synthetic batches and print {'step', 'val': {f1score_*/val, actions_loss/val, ...}} (train_pl.py:34: 500 "
+                         "there; 0 = off here)")
+    ap.add_argument("--eval_max_samples", type=int, default=1600, help="held-out trajectories per validation epoch, over all ranks (train_pl.py:33)")
     args = ap.parse_args()
     rank, local, world = parallel.init_from_env()
     torch.cuda.set_device(local)
@@ -79,6 +83,7 @@ def main():
     tr = ILTrainer(model, lr=args.lr)
     gen = torch.Generator(device=dev)
     gen.manual_seed(1234 + rank)
+    val_gen = torch.Generator(device=dev)
     B, T = args.per_gpu_batch, args.sliding_window
     steps = max(1, args.max_samples // (B * world))
     t0 = time.perf_counter()
@@ -95,6 +100,15 @@ def main():
         model.refresh_transposes()
         if rank == 0 and (it % max(1, steps // 8) == 0 or it == steps - 1):
             print(json.dumps({"step": it + 1, "loss": round(float(out["loss"]), 5)}), flush=True)
+        if args.eval_every and (it + 1) % args.eval_every == 0:
+            # the same held-out batches every time: a generator of its own, re-seeded, so that the training stream above is not advanced by a validation
+            val_gen.manual_seed(98765 + rank)
+            for _ in range(-(-args.eval_max_samples // (B * world))):
+                tr.validation_step(synthetic_batch(B, T, args.goal_tokens, dev, val_gen, args.raw_frames, feat_dim=model.dino_dim,
+                                                   siglip=model.text_encoder_name.startswith("SigLIP"), frame_hw=args.frame_hw))
+            val = tr.validation_epoch_end()                      # (a collective: every rank calls it)
+            if rank == 0:
+                print(json.dumps({"step": it + 1, "val": val}), flush=True)
         if rank == 0 and args.save_every and (it + 1) % args.save_every == 0:
             os.makedirs(args.output_dir, exist_ok=True)
             torch.save({"state_dict": {"model." + k: v.detach().cpu() for k, v in model.state_dict().items()}, "global_step": it + 1},
