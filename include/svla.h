@@ -552,6 +552,25 @@ int svla_policy_sample_rows_f32(const float* logits, long ld, const int* slot, c
 int svla_action_metrics_f32(const float* logits, long ld, const long* target, int rows, int A, long ignore_index, long long* counts, double* sums, int* pred,
                             void* stream);
 
+/* ---- batches of unequal-length trajectories: only the valid steps in front of the decoder ---------------------------------------------
+ * (Declared in front of the last section, as the section above is: only svla_attn_causal_fwd_bf16 moves, by two.)
+ * Preprocessor.process pads the trajectories of a batch to the longest with pad_sequence (architecture/models/transformer_models/preprocessors.py:101-107,246-303) and
+ * the reference's encoder then runs on every padded step (text_cond_visual_encoder.py:56-268); a padded step reaches no loss term (CrossEntropyLoss(ignore_index=-1),
+ * early_fusion_tsfm_models.py:93,115-117) and, padded at the end under a causal decoder, no valid step.  With il.EarlyFusionCnnTransformer(skip_padded_steps=True) the
+ * rows in front of the decoder are the valid steps only, "compact rows", ordered trajectory by trajectory (csrc/rows.hip).
+ * svla_rows_gather: for r < rows, the row_bytes bytes at dst + r * dst_stride = those at src + idx[r] * src_stride if 0 <= idx[r] < src_rows, else zeros.  Strides in
+ * bytes; the bytes between the rows of dst are not written.  idx int32 [rows] in device memory.  All accesses are 16-byte vectors.  One kernel for bytes of any type:
+ * uint8 frames and fp32 features out of the padded [B * T] batch, bf16 fusion outputs into decoder-row order (a padded step enters the decoder with a zero feature),
+ * and -- through the inverse table, the map being injective -- the decoder-input gradient back to compact rows, without atomics.
+ * SVLA_EINVAL, nothing launched: rows, src_rows or row_bytes <= 0, row_bytes or a stride not a multiple of 16, a stride below row_bytes, a NULL or not 16-byte
+ * aligned dst or src, a NULL idx.
+ * svla_fusion_text_bwd_seg: svla_fusion_text_bwd for compact rows: dtext[u, j, :] = sum over the rows r in [seg[u], seg[u + 1]) of dx0[r, text_off + j, :], fp32 sums
+ * of bf16 rows in row order, for u < U, j < L.  seg int32 [U + 1] in device memory, ascending, seg[U] <= the rows of dx0 [rows, S, D].  Plain stores (one wave owns
+ * its destination): bitwise repeatable; a goal without rows gets zeros.  SVLA_EINVAL, nothing launched: U or L <= 0, text_off < 0, text_off + L > S, D <= 0 or not a
+ * multiple of 8, a NULL pointer. */
+int svla_rows_gather(void* dst, long dst_stride, const void* src, long src_stride, const int* idx, int rows, long row_bytes, int src_rows, void* stream);
+int svla_fusion_text_bwd_seg(const svla_bf16* dx0, const int* seg, int U, int S, int L, int text_off, int D, float* dtext, void* stream);
+
 /* ---- causal attention over whole episodes ----------------------------------------------------------------------------------------
  * (Declared last: svla_replay_calls numbers the entry points in declaration order, and a new one must not move the others.)
  * The sequence form of the llama decoder's attention (llama/model.py:249-322 with the block-causal traj_index mask of early_fusion_tsfm_models.py:160-178, 491-497)

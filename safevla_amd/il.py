@@ -14,7 +14,9 @@ CLIP RN50 on 224 x 384, SigLIP on 256 x 256 frames or on camera frames resized t
 (``siglip_text.SigLIPTextFrozen``: ``goals`` is then the tokenizer's id tensor [B, 64], preprocessors.py:334-343).  ``state_dict`` uses the reference's names
 (``actor.weight``, no critic head), so Lightning checkpoints (``model.`` prefix) interchange.
 """
-from typing import Dict, Optional
+import contextlib
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -64,7 +66,7 @@ class EarlyFusionCnnTransformer(Tower):
 
     def __init__(self, device="cuda", max_length: int = 1000, input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"),
                  image_preprocessor=None, n_fusion_layers: int = 3, n_decoder_layers: int = 3, dino_dim: int = DINO, text_encoder: str = "t5-small", d_model: int = 512, n_heads: int = 8,
-                 n_heads_decoder: Optional[int] = None, data_augmentation: bool = False):
+                 n_heads_decoder: Optional[int] = None, data_augmentation: bool = False, skip_padded_steps: bool = False):
         if not torch.cuda.is_available():
             raise RuntimeError("safevla_amd needs an MI355X: there is no CPU or eager fallback for the policy kernels")
         ops.lib()
@@ -89,6 +91,9 @@ class EarlyFusionCnnTransformer(Tower):
             from .preproc import RandomDataAugmenter
             size = (256, 256) if text_encoder.startswith("SigLIP") else None
             self.augmenters = [RandomDataAugmenter(size=size) for _ in self.cameras]
+        # skip_padded_steps: a batch that holds ``lengths`` (int [B], the valid steps of each trajectory: ``Preprocessor.process`` below, preprocessors.py:294-296) runs
+        # everything in front of the decoder on the valid steps only (``prepare``).  Off, or without ``lengths``, or with every length equal to T: today's path.
+        self.skip_padded_steps = bool(skip_padded_steps)
         self._anchor = torch.zeros(1, device=device, requires_grad=True)
         self.sync_weights()
 
@@ -136,19 +141,37 @@ class EarlyFusionCnnTransformer(Tower):
         dev = self.device_
         B, T = batch[self.cameras[0]].shape[:2]
         R = T * B
+        rag = self._compact_rows(batch, B, T)                    # None: every step of the [B, T] batch runs (checked and built on the host, before the first launch)
         p = Prep()
         p.T, p.B, p.R = T, B, R
         p.acting = False                                         # forward(batch): whole windows, also when T = 1 (the agent's single steps set it)
-        p.tokens = torch.empty(R, self.ncam, NPATCH, self.dino_dim, device=dev, dtype=BF16)
+        Rf = R
+        if rag is not None:
+            # one upload per batch: decoder row -> compact row | compact row -> decoder row | compact row -> row (b * T + t) of the batch | goal of a compact row |
+            # first compact row of every goal
+            Rf = rag["Rf"]
+            tab = torch.from_numpy(rag["table"]).to(dev)
+            p.Rf, p.row_map, p.row_inv, row_src, gid_c, p.row_seg = (Rf,) + tuple(torch.split(tab, [R, Rf, Rf, Rf, B + 1]))
+        p.tokens = torch.empty(Rf, self.ncam, NPATCH, self.dino_dim, device=dev, dtype=BF16)
         for cam, key in enumerate(self.cameras):                 # only the model's sensors are read from the batch
             x = batch[key].to(dev)
             if x.dtype == torch.uint8:                           # raw frames [B,T,H,W,3] -> frozen ViT
                 if self.image_preprocessor is None:
                     self.image_preprocessor = self._frozen_image_encoder(key, dev)
                 if augment:
-                    x = self.augmenters[cam].augment_u8(x)
-                fr = x.transpose(0, 1).reshape(R, *x.shape[2:]).contiguous()
+                    x = self.augmenters[cam].augment_u8(x)       # (one transform per trajectory, drawn as without the skip: padded frames are augmented, then left behind)
+                if rag is not None:                              # the valid frames only, trajectory by trajectory, straight out of the [B * T] batch
+                    x, nb = x.contiguous(), x[0, 0].numel()
+                    fr = torch.empty(Rf, *x.shape[2:], device=dev, dtype=torch.uint8)
+                    ops.rows_gather(fr, nb, x, nb, row_src, Rf, nb, R)
+                else:
+                    fr = x.transpose(0, 1).reshape(R, *x.shape[2:]).contiguous()
                 self.image_preprocessor.process_tokens(fr, p.tokens, cam, ncam=self.ncam)
+            elif rag is not None:                                # pre-encoded features: the valid steps' [C, 84] fp32 rows; a padded step's are never read
+                x, nb = x.float().contiguous(), self.dino_dim * NPATCH * 4
+                ft = torch.empty(Rf, self.dino_dim, NPATCH, device=dev, dtype=F32)
+                ops.rows_gather(ft, nb, x, nb, row_src, Rf, nb, R)
+                ops.feat_to_tokens(ft, p.tokens, cam, ncam=self.ncam)
             else:                                                # pre-encoded features [B,T,384,7,12]
                 ops.feat_to_tokens(x.transpose(0, 1).reshape(R, self.dino_dim, NPATCH).contiguous().float(), p.tokens, cam, ncam=self.ncam)
         tb = lambda v: v.to(dev).transpose(0, 1).reshape(R).contiguous()     # [B,T] -> rows (t*B + b)
@@ -170,9 +193,42 @@ class EarlyFusionCnnTransformer(Tower):
             p.ids = (goals["input_ids"] if isinstance(goals, dict) else goals).to(dev).to(torch.int64).contiguous()
             p.attn_mask = torch.ones_like(p.ids)
             p.U, p.L = p.ids.shape[0], self.visual_encoder.text_encoder.out_tokens(p.ids.shape[1])
-        p.gid = (torch.arange(R, device=dev) % B).to(torch.int32).contiguous()
+        p.gid = (torch.arange(R, device=dev) % B).to(torch.int32).contiguous() if rag is None else gid_c
         p.S = self.text_off + p.L
         return p
+
+    def _compact_rows(self, batch: Dict, B: int, T: int):
+        """The host half of ``skip_padded_steps``: None when the batch runs as it always has (flag off, no ``lengths``, or every length equal to T); else the compact row
+        numbering -- the valid steps, trajectory by trajectory, so that one goal's rows are contiguous -- as one int32 table (``prepare`` names its parts).  Reads
+        ``lengths`` (the one host read the skip needs; none if it is a host tensor) and launches nothing; what cannot run is a ValueError here."""
+        if not self.skip_padded_steps or batch.get("lengths") is None:
+            return None
+        lens = np.asarray(torch.as_tensor(batch["lengths"]).reshape(-1).tolist(), dtype=np.int64)
+        if lens.shape[0] != B:
+            raise ValueError(f"lengths holds {lens.shape[0]} entries for a batch of {B} trajectories")
+        if lens.min() < 1 or lens.max() > T:
+            raise ValueError(f"lengths {lens.tolist()}: every trajectory has 1 ... {T} valid steps (T = the padded window)")
+        if (lens == T).all():
+            return None
+        goals = batch["goals"]
+        n_goals = int((goals["input_ids"] if isinstance(goals, dict) else goals).shape[0])
+        if n_goals != B:
+            raise ValueError(f"skip_padded_steps: {n_goals} goals for {B} trajectories (one goal per trajectory: a goal's compact rows are one segment)")
+        if self.fp8_attention or self.adt != BF16 or self._frame_rows_unaligned(batch):
+            raise ValueError("skip_padded_steps is not carried through fp8_attention, the fp32 verification mode, or uint8 frames whose H * W * 3 is not a multiple of "
+                             f"16 bytes (fp8_attention = {self.fp8_attention}, dtype = {self.adt}): build the model without the flag, or leave ``lengths`` out")
+        R, seg = T * B, np.concatenate([[0], np.cumsum(lens)])
+        Rf = int(seg[-1])
+        b_of = np.repeat(np.arange(B), lens)
+        t_of = np.arange(Rf) - seg[b_of]
+        inv = t_of * B + b_of                                    # compact row -> decoder row (t * B + b)
+        fwd = np.full(R, -1, dtype=np.int64)
+        fwd[inv] = np.arange(Rf)
+        return dict(Rf=Rf, table=np.concatenate([fwd, inv, b_of * T + t_of, b_of, seg]).astype(np.int32))
+
+    def _frame_rows_unaligned(self, batch: Dict) -> bool:
+        """a camera's uint8 frames whose bytes per frame the 16-byte row gather cannot take (the presets' 224 x 384 and 256 x 256 frames can)"""
+        return any(batch[k].dtype == torch.uint8 and batch[k][0, 0].numel() % 16 for k in self.cameras)
 
     def _frozen_image_encoder(self, key, dev):
         """IMAGE_ENCODERS of image_encoders.py:103-112 for raw uint8 frames, by preset: DINOv2 (224 x 384), the SigLIP trunk (256 x 256; other sizes are resized) or,
@@ -189,18 +245,28 @@ class EarlyFusionCnnTransformer(Tower):
 
     # ---- reference forward API --------------------------------------------------------------------------------------------------
     def _logits_tb(self, batch: Dict) -> torch.Tensor:
-        """The tower forward of a batch -> logits [T, B, A] fp32, rows in the kernels' order (t * B + b); shared by forward(batch) and ILTrainer.validation_step"""
+        """the logits of ``_forward_tb`` alone"""
+        return self._forward_tb(batch)[0]
+
+    def _targets_tb(self, batch: Dict, prep: Prep) -> torch.Tensor:
+        """``batch["actions"]`` as int64 rows (t * B + b).  With padded steps skipped, a padded step's target is the ignore index whatever the batch holds there (set on
+        the device from the row table): its logits come from a zero fusion feature and mean nothing."""
+        tgt = batch["actions"].to(self.device_).transpose(0, 1).reshape(-1).to(torch.int64)
+        return tgt if prep.row_map is None else torch.where(prep.row_map >= 0, tgt, torch.full_like(tgt, -1))
+
+    def _forward_tb(self, batch: Dict):
+        """The tower forward of a batch -> (logits [T, B, A] fp32, rows in the kernels' order (t * B + b); its Prep); shared by forward(batch) and ILTrainer.validation_step"""
         # whole episodes (512 < T <= 1000 steps) run forward only -- under torch.no_grad() or in eval mode; what cannot run is refused before the first launch
         self._check_seq_len(int(batch[self.cameras[0]].shape[1]), torch.is_grad_enabled() and self.training)
         prep = self.prepare(batch, augment=self.data_augmentation)
         logits, _, _ = _TowerFn.apply(self._anchor, self, prep, True, False)      # [T, B, A] fp32
-        return logits
+        return logits, prep
 
     def forward(self, batch: Dict) -> Dict[str, torch.Tensor]:
-        logits = self._logits_tb(batch)
+        logits, prep = self._forward_tb(batch)
         out = dict(actions_logits=logits.transpose(0, 1))
         if "actions" in batch:
-            tgt = batch["actions"].to(self.device_).transpose(0, 1).reshape(-1).to(torch.int64)
+            tgt = self._targets_tb(batch, prep)
             loss = _CEFn.apply(logits.reshape(-1, N_ACTIONS), tgt, -1)
             out["actions_loss"] = loss
             out["loss"] = loss
@@ -208,19 +274,19 @@ class EarlyFusionCnnTransformer(Tower):
 
     @classmethod
     def build_agent(cls, model_version="small_3", input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"), loss="action", device="cuda",
-                    sampling="greedy", data_augmentation: bool = False, ckpt_pth: Optional[str] = None, **kw):
+                    sampling="greedy", data_augmentation: bool = False, ckpt_pth: Optional[str] = None, skip_padded_steps: bool = False, **kw):
         """``build_agent`` of early_fusion_tsfm_models.py:352-363: the model of ``build_model`` wrapped in its online agent.  ``data_augmentation`` reaches the
         model's forward(batch) only: the agent's single steps act on the frames as they come."""
-        return EarlyFusionCnnTransformerAgent(cls.build_model(model_version, input_sensors, loss, data_augmentation, device=device, ckpt_pth=ckpt_pth), device,
-                                              sampling, **kw)
+        return EarlyFusionCnnTransformerAgent(cls.build_model(model_version, input_sensors, loss, data_augmentation, device=device, ckpt_pth=ckpt_pth,
+                                                              skip_padded_steps=skip_padded_steps), device, sampling, **kw)
 
     @classmethod
     def build_vector_agent(cls, model_version="small_3", input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"), loss="action", device="cuda",
                            sampling="greedy", num_episodes: int = 1, max_seq_len: int = 1000, tokenizer=None, generator: Optional[torch.Generator] = None,
-                           ckpt_pth: Optional[str] = None):
+                           ckpt_pth: Optional[str] = None, skip_padded_steps: bool = False):
         """The model of ``build_model`` behind ``EarlyFusionCnnTransformerVectorAgent``: ``num_episodes`` evaluation episodes served by one set of weights."""
-        return EarlyFusionCnnTransformerVectorAgent(cls.build_model(model_version, input_sensors, loss, device=device, ckpt_pth=ckpt_pth), num_episodes, device,
-                                                    sampling, max_seq_len=max_seq_len, tokenizer=tokenizer, generator=generator)
+        return EarlyFusionCnnTransformerVectorAgent(cls.build_model(model_version, input_sensors, loss, device=device, ckpt_pth=ckpt_pth,
+                                                                    skip_padded_steps=skip_padded_steps), num_episodes, device, sampling, max_seq_len=max_seq_len, tokenizer=tokenizer, generator=generator)
 
     @classmethod
     def version_config(cls, model_version):
@@ -231,17 +297,139 @@ class EarlyFusionCnnTransformer(Tower):
 
     @classmethod
     def build_model(cls, model_version="small_3", input_sensors=(NAV, MANIP, "last_actions", "an_object_is_in_hand"), loss="action",
-                    data_augmentation: bool = False, device="cuda", ckpt_pth: Optional[str] = None, ckpt_prefix: str = "model."):
+                    data_augmentation: bool = False, device="cuda", ckpt_pth: Optional[str] = None, ckpt_prefix: str = "model.", skip_padded_steps: bool = False):
         if model_version not in cls.VERSIONS:
             raise NotImplementedError(f"model_version {model_version!r}: built are {sorted(cls.VERSIONS)} (512-wide fusion transformer + llama decoder; "
                                       "early_fusion_tsfm_models.py:221-312)")
         nf, nd, dd, te, dm, nh, nhd = cls.version_config(model_version)
         m = cls(device=device, input_sensors=input_sensors, n_fusion_layers=nf, n_decoder_layers=nd, dino_dim=dd, text_encoder=te, d_model=dm, n_heads=nh,
-                n_heads_decoder=nhd, data_augmentation=data_augmentation)
+                n_heads_decoder=nhd, data_augmentation=data_augmentation, skip_padded_steps=skip_padded_steps)
         if ckpt_pth is not None:    # Lightning checkpoint (training/offline/train_utils.py:6-68)
             sd = torch.load(ckpt_pth, map_location="cpu")["state_dict"]
             m.load_state_dict({k[len(ckpt_prefix):]: v for k, v in sd.items() if k.startswith(ckpt_prefix)}, strict=False)
         return m
+
+
+def _default_action_list():
+    from .agent import ALL_STRETCH_ACTIONS
+    return list(ALL_STRETCH_ACTIONS)
+
+
+@dataclass
+class PreprocessorConfig:
+    """``PreprocessorConfig`` of preprocessors.py:63-73, for the fields that decide a batch here: ``max_steps`` (truncation), ``action_list``, ``goal_sensor_uuid``;
+    plus ``input_sensors`` (what the model was built for: ``model.input_sensors``) and ``text_encoder`` (the preset's, ``EarlyFusionCnnTransformer.version_config``).
+    The reference always pads (``pad = True`` is its only trained setting) and resizes / normalises the frames in this class (``image_size``, ``data_augmentation``):
+    here frames stay uint8 at the camera's size and both live in front of the frozen trunk (``EarlyFusionCnnTransformer(data_augmentation=...)``, preproc.py)."""
+    input_sensors: Sequence[str] = (NAV, MANIP, "last_actions", "an_object_is_in_hand")
+    max_steps: Optional[int] = None
+    action_list: List[str] = field(default_factory=_default_action_list)
+    goal_sensor_uuid: str = "goals"
+    text_encoder: str = "t5-small"
+    text_encoder_context_length: int = 64
+
+
+class Preprocessor:
+    """``Preprocessor.process`` of preprocessors.py:246-303 (the step in front of the model in ``LitModel.forward_batch``, train_pl.py:144-152): a list of samples
+    ``{"observations": {...}}`` of unequal length, as the dataset yields them, -> one padded batch for ``EarlyFusionCnnTransformer.forward`` / ``ILTrainer``.
+
+    Per key of the first sample's observations, in its order (:252-285):
+      a camera of ``input_sensors``   uint8 [t, H, W, 3] per sample -> uint8 [B, Tmax, H, W, 3], zero frames behind a trajectory's end (pad_sequence with 0, :101-107; the
+                                      reference pads the normalised float frames, here the frames stay uint8 and the trunk's front normalises them);
+      "actions"                       action strings -> int64 indices into ``action_list``, padding -1 (:120-136); an unknown string is a KeyError, as there;
+      "last_actions"                  the same vocabulary plus "" -> len(action_list) = 20, the start token (:80-83); padding len(action2idx) = 21 (:138-156);
+      "an_object_is_in_hand"          int64, padding 2 (:206-216);         "time_ids"    int64, padding -1 (:195-204);
+      "goal"                          -> ``cfg.goal_sensor_uuid``: strings through the tokenizer (t5 presets: ``tokenizer(goals, return_tensors="pt", padding=True)`` -> a dict
+                                      of input_ids / attention_mask, :158-164; SigLIP presets: ``tokenizer(goals, context_length=...)`` -> an id tensor, :334-343); goals
+                                      that are already tokenised (a dict of 1-D ids and mask, or a 1-D id tensor, per sample) pass through: right-padded with id 0 /
+                                      mask 0 to the longest (t5) or stacked (SigLIP);
+      "initial_agent_location", "templated_task_type"      ignored (:284);
+    and ``lengths`` int32 [B] with ``padding_mask`` bool [B, Tmax], True = padded (:241-244, 287-301).  Every per-step key is cut to ``max_steps`` first (:111,130,150,197,208).
+    The reference reports the UNCUT length of "actions" in ``lengths`` (:294-296); here it is the length after the cut, min(len, max_steps), so that ``lengths`` describes
+    the tensors next to it -- ``padding_mask`` is the same either way.  Without "actions" the length is read from the first camera (the reference picks a random one, :290-292).
+
+    The keys follow the model: a camera, "last_actions" or "an_object_is_in_hand" that ``input_sensors`` does not list, or any key the reference's ``process`` knows
+    (visibility, rooms_seen, the bbox sensors, relative_arm_location_metadata, ...) or does not know, is a ValueError that names it (the reference: NotImplementedError
+    for the unknown, :283-285).  Works on ``device="cpu"``."""
+
+    _ALWAYS, _IGNORED = ("actions", "goal", "time_ids"), ("initial_agent_location", "templated_task_type")
+
+    def __init__(self, cfg: Optional[PreprocessorConfig] = None, device="cuda", tokenizer=None):
+        self.cfg = cfg = cfg if cfg is not None else PreprocessorConfig()
+        self.device = torch.device(device)
+        self.cameras, self.has_hand, self.has_prev = sensor_set(cfg.input_sensors)
+        self.action2idx = {a: i for i, a in enumerate(cfg.action_list)}
+        self.action2idx[""] = len(cfg.action_list)               # start-of-sequence token of last_actions (:81-83)
+        if tokenizer is None and cfg.text_encoder == "t5-small":
+            from .text import GoalTokenizer
+            tokenizer = GoalTokenizer()
+        self.tokenizer = tokenizer
+
+    @property
+    def num_actions(self):
+        return len(self.action2idx)
+
+    def _pad(self, rows, value):
+        return torch.nn.utils.rnn.pad_sequence(rows, batch_first=True, padding_value=value).to(self.device)
+
+    def _steps(self, batch, key, value, dtype=torch.int64):
+        return self._pad([torch.as_tensor(np.asarray(s[key][:self.cfg.max_steps])).to(dtype).reshape(-1) for s in batch], value)
+
+    def _words(self, batch, key, value):
+        return self._pad([torch.tensor([self.action2idx[a] for a in s[key][:self.cfg.max_steps]], dtype=torch.int64) for s in batch], value)
+
+    def _frames(self, batch, key):
+        frames = [torch.as_tensor(s[key][:self.cfg.max_steps]) for s in batch]
+        if any(f.dtype != torch.uint8 or f.dim() != 4 or f.shape[-1] != 3 for f in frames):
+            raise ValueError(f"{key}: uint8 frames [t, H, W, 3] per sample, got {[(str(f.dtype), tuple(f.shape)) for f in frames][:3]}")
+        return self._pad(frames, 0)
+
+    def _goals(self, batch):
+        goals = [s["goal"] for s in batch]
+        t5 = self.cfg.text_encoder == "t5-small"
+        if all(isinstance(g, str) for g in goals):
+            if self.tokenizer is None:
+                raise ValueError("string goals need a tokenizer (SigLIP presets: open_clip's tokenizer is not available offline; pass tokenised goals or tokenizer=)")
+            if t5:
+                return {k: v.to(self.device) for k, v in self.tokenizer(goals, return_tensors="pt", padding=True).items()}
+            return torch.as_tensor(self.tokenizer(goals, context_length=self.cfg.text_encoder_context_length)).to(self.device)
+        if any(isinstance(g, str) for g in goals):
+            raise ValueError("goals: strings and tokenised goals in one batch")
+        one = lambda v: torch.as_tensor(np.asarray(v)).to(torch.int64).reshape(-1)
+        if all(isinstance(g, dict) for g in goals):
+            return {k: self._pad([one(g[k]) for g in goals], 0) for k in ("input_ids", "attention_mask")}
+        ids = [one(g) for g in goals]
+        if t5:                                                       # bare ids for a t5 preset: the mask is where they are
+            return dict(input_ids=self._pad(ids, 0), attention_mask=self._pad([torch.ones_like(i) for i in ids], 0))
+        return torch.stack(ids).to(self.device)
+
+    def process(self, batch):
+        if len(batch) == 0:
+            return None
+        batch = [s["observations"] for s in batch]
+        keys, out = list(batch[0].keys()), dict()
+        for key in keys:
+            if key in self.cameras:
+                out[key] = self._frames(batch, key)
+            elif key == "an_object_is_in_hand" and self.has_hand:
+                out[key] = self._steps(batch, key, 2)
+            elif key == "last_actions" and self.has_prev:
+                out[key] = self._words(batch, key, len(self.action2idx))
+            elif key == "actions":
+                out[key] = self._words(batch, key, -1)
+            elif key == "time_ids":
+                out[key] = self._steps(batch, key, -1)
+            elif key == "goal":
+                out[self.cfg.goal_sensor_uuid] = self._goals(batch)
+            elif key not in self._IGNORED:
+                raise ValueError(f"sensor {key!r}: the model is built for {list(self.cfg.input_sensors)} (+ {list(self._ALWAYS)}; ignored: {list(self._IGNORED)})")
+        look = "actions" if "actions" in keys else next((k for k in keys if k in self.cameras), None)
+        if look is None:
+            raise ValueError(f"samples hold neither 'actions' nor a camera of {list(self.cameras)}: no length to read")
+        cut = self.cfg.max_steps
+        out["lengths"] = torch.tensor([len(s[look]) if cut is None else min(len(s[look]), cut) for s in batch], dtype=torch.int32).to(self.device)
+        out["padding_mask"] = torch.arange(out[look].shape[1], device=self.device)[None, :] >= out["lengths"][:, None]
+        return out
 
 
 def f1_from_counts(C) -> Dict:
@@ -308,13 +496,36 @@ class ActionF1:
         self.state.zero_()
 
 
+@contextlib.contextmanager
+def deterministic_gradients(model: EarlyFusionCnnTransformer, n_rows: int):
+    """Inside, the backward of ``model`` accumulates its gradients across workgroups as 64-bit fixed-point integers in a shadow of the flat gradient buffer
+    (svla_det_config: integer addition is associative, so two passes over the same inputs leave the same bits); on leaving, the shadow is folded into
+    ``model.arena.flat_g`` and unregistered.  ``n_rows``: the steps of the batch, which sets the shadow's grid as the RL engine does (``ops.det_grid_bits``: the
+    partial sums of a mean over fewer rows are larger).  ``ops.det_bypass_count()`` afterwards tells how many partials were too large for the shadow (0: repeatable)."""
+    g = model.arena.flat_g
+    shadow = getattr(model, "_det_shadow", None)
+    if shadow is None or shadow.numel() != g.numel():
+        shadow = model._det_shadow = torch.zeros(g.numel(), device=g.device, dtype=torch.int64)
+    ops.det_set_grid(ops.det_grid_bits(n_rows))
+    ops.det_config(0, g, shadow)
+    try:
+        yield
+    finally:
+        ops.det_finalize(g, shadow)
+        ops.det_config(0, None, None)
+
+
 class ILTrainer:
     """``LitModel.training_step`` + ``configure_optimizers`` (training/offline/train_pl.py:154-186,283-287): AdamW(lr) on the flat arena; and its
     ``validation_step`` / ``on_validation_epoch_end`` (:187-281) on the F1 state of ``ActionF1``."""
 
-    def __init__(self, model: EarlyFusionCnnTransformer, lr: float = 1e-4, weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8):
+    def __init__(self, model: EarlyFusionCnnTransformer, lr: float = 1e-4, weight_decay: float = 0.01, betas=(0.9, 0.999), eps: float = 1e-8,
+                 deterministic: bool = False):
         self.model, self.lr, self.wd, self.betas, self.eps = model, lr, weight_decay, betas, eps
         self.step_count = 0
+        # deterministic: bitwise-repeatable gradients -- every cross-workgroup accumulation of the backward in 64-bit fixed point (``deterministic_gradients``), as
+        # PPOLagConfig(deterministic=True) does for the RL update
+        self.deterministic = bool(deterministic)
         self.val_metrics = ActionF1(N_ACTIONS, -1, device=model.device_)
 
     def validation_step(self, batch: Dict) -> None:
@@ -326,8 +537,8 @@ class ILTrainer:
         m.eval()
         try:
             with torch.no_grad():
-                logits = m._logits_tb(batch)
-                tgt = batch["actions"].to(m.device_).transpose(0, 1).reshape(-1).to(torch.int64)      # rows (t * B + b), as forward(batch) orders them
+                logits, prep = m._forward_tb(batch)
+                tgt = m._targets_tb(batch, prep)                      # rows (t * B + b), as forward(batch) orders them
                 self.val_metrics.update(logits.reshape(-1, N_ACTIONS), tgt)
         finally:
             m.train(was_training)
@@ -351,8 +562,14 @@ class ILTrainer:
     def training_step(self, batch: Dict) -> Dict[str, float]:
         m = self.model
         m.zero_grad()
-        out = m(batch)
-        out["loss"].backward()
+        if self.deterministic:
+            B, T = batch[m.cameras[0]].shape[:2]
+            with deterministic_gradients(m, B * T):
+                out = m(batch)
+                out["loss"].backward()
+        else:
+            out = m(batch)
+            out["loss"].backward()
         self.step_count += 1
         ar = m.arena
         ops.adam_step(ar.flat_p, ar.flat_g, ar.flat_m, ar.flat_v, ar.flat_bf16, self.lr, self.step_count, self.betas[0], self.betas[1],

@@ -418,6 +418,10 @@ class Tower(nn.Module):
             raise ValueError("row_pos / row_klen: the acting step on per-row KV rings is a T = 1 forward without gradients, with both fields given")
         if prep.fusion_kvalid is not None and (need_grad or self.fp8_attention):
             raise ValueError("fusion_kvalid: the key-padding mask of the fusion encoder exists in the bf16 / fp32 forward only (no backward, no fp8 form)")
+        ragged = prep.row_map is not None
+        if ragged and (prep.acting or per_row or prep.fusion_kvalid is not None or self.fp8_attention or self.adt != BF16 or prep.row_inv is None or prep.row_seg is None):
+            raise ValueError("row_map: compact fusion rows exist for forward(batch) on the bf16 path (no acting step, fusion_kvalid, fp8_attention or fp32 mode), "
+                             "with row_inv and row_seg given")
         if not per_row and (T > 1 or need_grad or not prep.acting or self.time_step_counter >= self.max_steps):
             self.time_step_counter = 0
         seed, site = self._drop_sites()
@@ -430,8 +434,14 @@ class Tower(nn.Module):
                 c["fusion"].append(saved)
         # decoder over the rollout time axis, rows (b*T + t); a pruned last fusion layer left the position-0 rows only
         xd = torch.empty(prep.R, D, device=self.device_, dtype=self.adt)
+        ldx, x0 = (D if nfl and self.prune_last else S * D), xf
+        if ragged:
+            # compact rows -> decoder-row order (t * B + b); a padded step gets a zero feature, its embedding terms are added below as usual
+            x0, es = torch.empty(prep.R, D, device=self.device_, dtype=self.adt), xf.element_size()
+            ops.rows_gather(x0, D * es, xf, ldx * es, prep.row_map, prep.R, D * es, prep.Rf)
+            ldx = D
         # an absent sensor's table and indices go in as None together (svla_decoder_embed_fwd: the term is skipped)
-        ops.decoder_embed_fwd(xf, D if nfl and self.prune_last else S * D, self.last_actions_embed.weight if self.has_prev else None,
+        ops.decoder_embed_fwd(x0, ldx, self.last_actions_embed.weight if self.has_prev else None,
                               self.object_in_hand_embed.weight if self.has_hand else None, self.time_encoder.div_term,
                               prep.prev_actions if self.has_prev else None, prep.masks if self.has_prev else None, prep.hand if self.has_hand else None,
                               prep.time_step, T, B, xd)
@@ -448,7 +458,7 @@ class Tower(nn.Module):
 
     def _inputs_fwd(self, prep, c, need_grad):
         """Visual compressor + adapter (all cameras), frozen text encoder + text adapter, ``fusion_fill`` -> the fusion transformer's input rows [R * S, D]"""
-        D, R, S, L, U, ve, w = self.D, prep.R, prep.S, prep.L, prep.U, self.visual_encoder, self._w
+        D, R, S, L, U, ve, w = self.D, prep.Rf, prep.S, prep.L, prep.U, self.visual_encoder, self._w      # R: fusion rows (all decoder rows, or the valid steps only)
         if S != self.text_off + L or prep.tokens.numel() != R * self.ncam * NPATCH * self.dino_dim:
             raise ValueError(f"inputs of {prep.tokens.numel() // max(R * NPATCH * self.dino_dim, 1)} camera(s), S = {S} for a tower of {self.ncam} camera(s), S = {self.text_off + L}")
         M2 = R * self.ncam * NPATCH
@@ -479,7 +489,7 @@ class Tower(nn.Module):
     def _fusion_layer_fwd(self, i, xf, prep, site, need_grad):
         """Fusion layer ``i`` on the token rows ``xf`` [R * S, D] -> (output rows, saved activations or None).  Its attention half has four forms (absorbed single
         query, single query over materialised K / V, fp8, full QKV) that meet at ``ao``; the rest of the layer is ``_fusion_post_fwd``."""
-        D, H, R, S, w, SCF = self.D, self.H, prep.R, prep.S, self._w, self.hdim ** -0.5          # SCF: 0.125 for 64-wide heads
+        D, H, R, S, w, SCF = self.D, self.H, prep.Rf, prep.S, self._w, self.hdim ** -0.5         # SCF: 0.125 for 64-wide heads; R: fusion rows
         M, l = R * S, self.visual_encoder.fusion_xformer.layers[i]
         if self.prune_last and i == len(self.visual_encoder.fusion_xformer.layers) - 1:
             # Only sequence position 0 of the last fusion layer is consumed (allenact_dino_transformer.py:708 x[:, 0]): Q / attention / out_proj / norm1 / FFN /
@@ -736,16 +746,24 @@ class Tower(nn.Module):
         """Accumulates parameter gradients into the arena's flat grad buffer.  ``dfull_logits``: gradient of the discrete critic's
         bin logits (HL-Gauss loss), critic_type == "discrete" only."""
         D, T, B, R, S, g = self.D, prep.T, prep.B, prep.R, prep.S, self.g
+        Rf, ragged = prep.Rf, prep.row_map is not None
         dx = self._heads_bwd(prep, c, dlogits, dvalues, dfull_logits)
         if dx is None:
             return
         dx = self._decoder_seq_bwd(prep, c, dx)
         # gradient of the fusion transformer's output: the position-0 rows only behind a pruned last layer, else all token rows (zero but for position 0)
         pruned = bool(c["fusion"]) and c["fusion"][-1]["pruned"]
-        dyf = torch.empty(R, D, device=self.device_, dtype=self.adt) if pruned else ops.zeros(R, S, D, device=self.device_, dtype=self.adt).view(R * S, D)
+        dyf = torch.empty(Rf, D, device=self.device_, dtype=self.adt) if pruned else ops.zeros(Rf, S, D, device=self.device_, dtype=self.adt).view(Rf * S, D)
+        ldy = D if pruned else S * D
+        # compact fusion rows: the kernel leaves the decoder-input gradient in decoder-row order (the embedding tables take every row's, a padded step's is zero), and
+        # the inverse table brings the valid steps' rows back -- a gather, the map being injective
+        dyr = torch.empty(R, D, device=self.device_, dtype=self.adt) if ragged else dyf
         ops.decoder_embed_bwd(dx, prep.prev_actions if self.has_prev else None, prep.masks if self.has_prev else None, prep.hand if self.has_hand else None, T, B,
-                              dyf, D if pruned else S * D, g(self.last_actions_embed.weight) if self.has_prev else None,
+                              dyr, D if ragged else ldy, g(self.last_actions_embed.weight) if self.has_prev else None,
                               g(self.object_in_hand_embed.weight) if self.has_hand else None)
+        if ragged:
+            es = dyr.element_size()
+            ops.rows_gather(dyf, ldy * es, dyr, D * es, prep.row_inv, Rf, D * es, R)
         site = self._site_fn(c.get("drop_seed"))
         drop_scale = 1.0 / (1.0 - self.dropout_p) if c.get("drop_seed") is not None else 1.0
         for i in reversed(range(len(c["fusion"]))):
@@ -823,7 +841,7 @@ class Tower(nn.Module):
 
     def _fusion_layer_bwd(self, i, a, dyf, prep, site, drop_scale):
         """Backward of fusion layer ``i``: the gradient of its output rows -> the gradient of its input rows [R * S, D]"""
-        D, H, R, S, w, wt, dw, g, SCF = self.D, self.H, prep.R, prep.S, self._w, self._wt, self._dw, self.g, self.hdim ** -0.5
+        D, H, R, S, w, wt, dw, g, SCF = self.D, self.H, prep.Rf, prep.S, self._w, self._wt, self._dw, self.g, self.hdim ** -0.5      # R: fusion rows
         M, l = R * S, self.visual_encoder.fusion_xformer.layers[i]
         if a["pruned"]:
             dao, dh1 = self._fusion_post_bwd(i, a, dyf, R, S, site, drop_scale)
@@ -867,13 +885,16 @@ class Tower(nn.Module):
 
     def _inputs_bwd(self, prep, c, dx0):
         """backward of ``_inputs_fwd``: gradient of the fusion transformer's input rows -> fusion token, text adapter (frozen text encoder), visual adapter + compressor"""
-        D, T, B, R, S, L, U = self.D, prep.T, prep.B, prep.R, prep.S, prep.L, prep.U
+        D, T, B, R, S, L, U = self.D, prep.T, prep.B, prep.Rf, prep.S, prep.L, prep.U      # R: fusion rows
         ve, wt, dw, g, dev = self.visual_encoder, self._wt, self._dw, self.g, self.device_
         M2 = R * self.ncam * NPATCH
         ops.colsum_acc(dx0, g(ve.fusion_token), R, D, row_stride=S)
         # text adapter (trainable) -- the T5 encoder is frozen (no_grad in the reference)
         dtf = ops.zeros(U * L, D, device=dev, dtype=F32)
-        if ops.det_active():       # deterministic mode: this accumulated intermediate gets its own fixed-point shadow (slot 1)
+        if prep.row_seg is not None:
+            # compact rows lie goal by goal: the segmented form, one wave per (goal, token) over that goal's rows, plain stores (repeatable without a shadow)
+            ops.fusion_text_bwd_seg(dx0, prep.row_seg, U, S, L, self.text_off, dtf)
+        elif ops.det_active():       # deterministic mode: this accumulated intermediate gets its own fixed-point shadow (slot 1)
             dtf_sh = torch.zeros(U * L * D, device=dev, dtype=torch.int64)
             ops.det_config(1, dtf, dtf_sh)
             try:
@@ -1021,13 +1042,29 @@ class Prep:
     ``row_pos``, ``row_klen`` (int32 [B], given together) and ``row_cache`` (int32 [B] or None = identity): the acting step on per-row KV rings -- row b writes slot
     row_pos[b] of cache row row_cache[b] and attends to that cache row's first row_klen[b] slots; the tower's own step counter takes no part.  ``row_window`` (int W)
     and ``row_slide`` (int): with a window every row's decoder input is kept in a history ring of W slots, and the trailing row_slide rows -- episodes that have
-    outlived W steps -- are decoded anew over their last W steps instead of against the KV ring."""
+    outlived W steps -- are decoded anew over their last W steps instead of against the KV ring.
+    ``Rf``, ``row_map``, ``row_inv``, ``row_seg`` (given together; the imitation-learning model's batches of unequal-length trajectories): everything in front of the
+    decoder runs on Rf <= R "compact" rows -- the valid steps, trajectory by trajectory -- so tokens is [Rf, ...] and gid [Rf]; row_map int32 [R]: decoder row
+    (t * B + b) -> its compact row, or -1 for a padded step (which enters the decoder with a zero fusion feature); row_inv int32 [Rf]: the inverse; row_seg int32
+    [U + 1]: goal u owns the compact rows row_seg[u] ... row_seg[u + 1].  The decoder-side fields (prev_actions ... time_step, traj_bt) stay [R].  Update passes on the
+    bf16 path only.  The RL towers never set them: Rf = R."""
     __slots__ = ("T", "B", "R", "S", "L", "U", "tokens", "prev_actions", "masks", "hand", "time_step", "traj_bt", "ids", "attn_mask", "gid",
-                 "acting", "ids_key", "attn_mask_u8", "kvalid_static", "fusion_kvalid", "row_cache", "row_pos", "row_klen", "row_window", "row_slide")
+                 "acting", "ids_key", "attn_mask_u8", "kvalid_static", "fusion_kvalid", "row_cache", "row_pos", "row_klen", "row_window", "row_slide",
+                 "_Rf", "row_map", "row_inv", "row_seg")
 
     def __init__(self):
         self.acting, self.ids_key, self.attn_mask_u8, self.kvalid_static = True, None, None, None
         self.fusion_kvalid = self.row_cache = self.row_pos = self.row_klen = self.row_window = self.row_slide = None
+        self._Rf = self.row_map = self.row_inv = self.row_seg = None
+
+    @property
+    def Rf(self):
+        """rows in front of the decoder (fusion rows); R unless a producer set fewer (il.EarlyFusionCnnTransformer.prepare with skip_padded_steps)"""
+        return self.R if self._Rf is None else self._Rf
+
+    @Rf.setter
+    def Rf(self, n):
+        self._Rf = n
 
 
 class _ActingState(Prep):

@@ -656,6 +656,41 @@ def rows_add(dst, dst_ld, src, src_ld, rows, D=512):
     lib().call("svla_rows_add_f32" if dst.dtype == F32 else "svla_rows_add_bf16", _p(dst), dst_ld, _p(src), src_ld, rows, D, _stream())
 
 
+def _bytes_behind(t: torch.Tensor) -> int:
+    """bytes of ``t``'s storage from its first element on"""
+    return t.untyped_storage().nbytes() - t.storage_offset() * t.element_size()
+
+
+def rows_gather(dst, dst_stride, src, src_stride, idx, rows, row_bytes, src_rows):
+    """svla_rows_gather (csrc/rows.hip): for r < rows, the ``row_bytes`` bytes at dst + r * dst_stride = those at src + idx[r] * src_stride, zeros where idx[r] is
+    outside [0, src_rows).  Strides in BYTES; any dtype (the rows are copied as 16-byte vectors); idx int32 [>= rows] on the device.  Both extents are checked against
+    the tensors' storage here, so that no index the kernel accepts leaves them."""
+    _chk(idx, torch.int32, "idx")
+    rows, row_bytes, src_rows, dst_stride, src_stride = int(rows), int(row_bytes), int(src_rows), int(dst_stride), int(src_stride)
+    if not (dst.is_cuda and src.is_cuda) or dst.device != src.device or idx.device != src.device:
+        raise ValueError("rows_gather: dst, src and idx must be tensors of one GPU (no CPU fallback)")
+    if rows <= 0 or src_rows <= 0 or row_bytes <= 0 or row_bytes % 16 or dst_stride % 16 or src_stride % 16 or dst_stride < row_bytes or src_stride < row_bytes:
+        raise ValueError(f"rows_gather: rows = {rows}, src_rows = {src_rows}, row_bytes = {row_bytes} (a positive multiple of 16), strides {dst_stride} / {src_stride} "
+                         "(multiples of 16, not below row_bytes)")
+    if idx.numel() < rows or not idx.is_contiguous():
+        raise ValueError(f"rows_gather: idx holds {idx.numel()} contiguous entries for {rows} rows")
+    if (rows - 1) * dst_stride + row_bytes > _bytes_behind(dst) or (src_rows - 1) * src_stride + row_bytes > _bytes_behind(src):
+        raise ValueError(f"rows_gather: {rows} rows of stride {dst_stride} / {src_rows} rows of stride {src_stride} do not fit dst ({_bytes_behind(dst)} bytes) / "
+                         f"src ({_bytes_behind(src)} bytes)")
+    lib().call("svla_rows_gather", _p(dst), dst_stride, _p(src), src_stride, _p(idx), rows, row_bytes, src_rows, _stream())
+
+
+def fusion_text_bwd_seg(dx0, seg, U, S, L, text_off, dtext):
+    """svla_fusion_text_bwd_seg (csrc/rows.hip): dtext[u, j] = the sum of dx0[r, text_off + j] over the compact rows r in [seg[u], seg[u + 1]); bf16 rows, fp32 sums"""
+    _chk(dx0, BF16, "dx0")
+    _chk(seg, torch.int32, "seg")
+    _chk(dtext, F32, "dtext")
+    D = int(dtext.shape[-1])
+    if seg.numel() != U + 1 or dtext.numel() != U * L * D or dx0.numel() % (S * D):
+        raise ValueError(f"fusion_text_bwd_seg: seg [{seg.numel()}] for {U} goals, dtext {tuple(dtext.shape)} for [{U}, {L}, {D}], dx0 {tuple(dx0.shape)} in rows of {S} x {D}")
+    lib().call("svla_fusion_text_bwd_seg", _p(dx0), _p(seg), U, S, L, text_off, D, _p(dtext), _stream())
+
+
 def zeros(*shape, device, dtype):
     """torch.zeros through the C ABI (allocation by torch, the fill is a recorded launch)."""
     t = torch.empty(*shape, device=device, dtype=dtype)

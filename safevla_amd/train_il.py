@@ -42,7 +42,7 @@ def synthetic_batch(B: int, T: int, L: int, device, generator: torch.Generator, 
     if siglip:
         ids64 = torch.ones(B, 64, device=device, dtype=ids.dtype)
         ids64[:, :L] = torch.where(am > 0, ids, torch.ones_like(ids))
-    return {NAV: nav, MANIP: man, "time_ids": tt.contiguous(), "padding_mask": pad, "last_actions": last, "actions": actions,
+    return {NAV: nav, MANIP: man, "time_ids": tt.contiguous(), "padding_mask": pad, "lengths": valid.to(torch.int32), "last_actions": last, "actions": actions,
             "an_object_is_in_hand": r(B, T, hi=3), "goals": ids64 if siglip else dict(input_ids=ids, attention_mask=am)}
 
 
@@ -64,6 +64,8 @@ def main():
     ap.add_argument("--data_augmentation", action="store_true",
                     help="with --raw_frames: the random v2 frame augmentation, one newly drawn transform per trajectory and camera (the reference trains with it on "
                          "unless --no_augmentation, train_pl.py:92; off here unless asked for)")
+    ap.add_argument("--skip_padded_steps", action="store_true",
+                    help="run everything in front of the decoder on the valid steps of a batch only (its ``lengths``); off: every padded step runs, as in the reference")
     ap.add_argument("--init_ckpt", default=None)
     ap.add_argument("--eval_every", type=int, default=0,
                     help="validate every N steps on held-out synthetic batches and print {'step', 'val': {f1score_*/val, actions_loss/val, ...}} (train_pl.py:34: 500 "
@@ -73,7 +75,8 @@ def main():
     rank, local, world = parallel.init_from_env()
     torch.cuda.set_device(local)
     dev = torch.device("cuda", local)
-    model = EarlyFusionCnnTransformer.build_model(args.model_version, args.input_sensors, args.loss, args.data_augmentation, device=dev, ckpt_pth=args.init_ckpt)
+    model = EarlyFusionCnnTransformer.build_model(args.model_version, args.input_sensors, args.loss, args.data_augmentation, device=dev, ckpt_pth=args.init_ckpt,
+                                                  skip_padded_steps=args.skip_padded_steps)
     if args.data_augmentation:
         for cam, a in enumerate(model.augmenters):
             a.generator = torch.Generator().manual_seed(4321 + 2 * rank + cam)
