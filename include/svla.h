@@ -243,9 +243,15 @@ int svla_acting_stage(const void* tok_src, void* tok_dst, long tok_bytes, const 
  * workgroup_id_z picks the member's argument block -- on `stream`, falling back to one launch per member wherever the members' launches differ in
  * anything but their arguments (and for kernels without a grouped twin: csrc/launch.h lists how a kernel takes part).  Results are bit-identical
  * to the per-member launches (same kernels, same arithmetic, same grids per member).  A capture belongs to the calling thread; captures do not nest.
+ * ORDER: the launches of one member reach the stream in the order its calls made them -- a launch that cannot be kept (a kernel without a grouped twin, an assembly
+ * kernel, a memset, a copy) is issued at once, behind the member's launches kept so far, which are issued singly for it; what is left comes out at svla_group_end,
+ * member by member.  Nothing orders one member's launches against another's.  STREAM: the first launch made inside a capture fixes the capture's stream; an entry
+ * point called with another one returns SVLA_EINVAL and launches nothing, and svla_group_end(another one) returns SVLA_EINVAL, issues nothing and closes the
+ * capture.  An empty capture ends on any stream.
  * svla_replay_calls_grouped replays `members` recorded sequences that name the same entry points in the same order (args[m] = member m's argument
  * words, laid out as for svla_replay_calls) as begin / member calls / end per call index: the acting step of the three towers becomes one dependency
- * chain of grouped launches instead of three streams.  svla_group_stats: launches issued grouped / singly by this thread's captures since the last call. */
+ * chain of grouped launches instead of three streams.  svla_group_stats: grouped issues / launches issued singly by this thread's captures since the last call (every kept launch is counted once;
+ * launches that were never kept are not counted). */
 int svla_group_begin(int members);
 int svla_group_member(int member);
 int svla_group_end(void* stream);

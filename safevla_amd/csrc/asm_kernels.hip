@@ -50,6 +50,7 @@ int svla_asm_launch2(const char* name, const void* kernarg, size_t kernarg_bytes
         if (it == g_fn.end()) return SVLA_EINVAL;
         f = it->second;
     }
+    if (const int rc = svla_direct(stream)) return rc;      // a capture's pending launches of this member go first (launch.h)
     size_t sz = kernarg_bytes;
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, (void*)kernarg, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
     HIP_CHECK_RET(hipModuleLaunchKernel(f, grid_x, grid_y, 1, block, 1, 1, 0, stream, nullptr, extra));

@@ -490,12 +490,11 @@ extern "C" int svla_attn_fp8_quant(const bf16_t* qkv, long ld, int rows, int S, 
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(rows * H * 3), block(F8_THREADS);
     switch (f8_nkt(S)) {
-        case 4: hipLaunchKernelGGL((attn_fp8_quant_kernel<64>), grid, block, 0, st, qkv, ld, S, H, ws, scales); break;
-        case 8: hipLaunchKernelGGL((attn_fp8_quant_kernel<128>), grid, block, 0, st, qkv, ld, S, H, ws, scales); break;
-        case 12: hipLaunchKernelGGL((attn_fp8_quant_kernel<192>), grid, block, 0, st, qkv, ld, S, H, ws, scales); break;
-        default: hipLaunchKernelGGL((attn_fp8_quant_kernel<256>), grid, block, 0, st, qkv, ld, S, H, ws, scales); break;
+        case 4: return svla_launch<attn_fp8_quant_kernel<64>>(grid, block, 0, st, qkv, ld, S, H, ws, scales);
+        case 8: return svla_launch<attn_fp8_quant_kernel<128>>(grid, block, 0, st, qkv, ld, S, H, ws, scales);
+        case 12: return svla_launch<attn_fp8_quant_kernel<192>>(grid, block, 0, st, qkv, ld, S, H, ws, scales);
+        default: return svla_launch<attn_fp8_quant_kernel<256>>(grid, block, 0, st, qkv, ld, S, H, ws, scales);
     }
-    return svla_launch_status();
 }
 
 template <int NKT>
@@ -533,13 +532,13 @@ extern "C" int svla_attn_fp8_bwd(const unsigned char* ws, const float* scales, c
     if (head_dim != HD || rows <= 0 || S <= 0 || S > 256 || H <= 0 || (ldo % 8) || (lddo % 8) || (ldd % 4)) return SVLA_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     const dim3 grid(rows * H), block(F8_THREADS);
+    int rc;
     switch (f8_nkt(S)) {
-        case 4: hipLaunchKernelGGL((attn_fp8_bwd_prep_kernel<64>), grid, block, 0, st, dO, lddo, O, ldo, S, H, gws, gscale, D); break;
-        case 8: hipLaunchKernelGGL((attn_fp8_bwd_prep_kernel<128>), grid, block, 0, st, dO, lddo, O, ldo, S, H, gws, gscale, D); break;
-        case 12: hipLaunchKernelGGL((attn_fp8_bwd_prep_kernel<192>), grid, block, 0, st, dO, lddo, O, ldo, S, H, gws, gscale, D); break;
-        default: hipLaunchKernelGGL((attn_fp8_bwd_prep_kernel<256>), grid, block, 0, st, dO, lddo, O, ldo, S, H, gws, gscale, D); break;
+        case 4: rc = svla_launch<attn_fp8_bwd_prep_kernel<64>>(grid, block, 0, st, dO, lddo, O, ldo, S, H, gws, gscale, D); break;
+        case 8: rc = svla_launch<attn_fp8_bwd_prep_kernel<128>>(grid, block, 0, st, dO, lddo, O, ldo, S, H, gws, gscale, D); break;
+        case 12: rc = svla_launch<attn_fp8_bwd_prep_kernel<192>>(grid, block, 0, st, dO, lddo, O, ldo, S, H, gws, gscale, D); break;
+        default: rc = svla_launch<attn_fp8_bwd_prep_kernel<256>>(grid, block, 0, st, dO, lddo, O, ldo, S, H, gws, gscale, D); break;
     }
-    int rc = svla_launch_status();
     if (rc) return rc;
     Fp8Args p{};
     p.ws = ws; p.sc = scales; p.gws = gws; p.sg = gscale; p.D = D; p.LSE = (float*)LSE; p.dQ = dQ; p.dK = dK; p.dV = dV; p.ldd = ldd;

@@ -321,11 +321,9 @@ __global__ void __launch_bounds__(256) head_pick_kernel(const bf16_t* __restrict
 
 extern "C" int svla_head_expand_bf16(const bf16_t* v, long ldv, int R, bf16_t* E, const float* bias, float* dot, const float* sigma, bf16_t* vs, void* stream) {
     if (!v || !E || R <= 0 || ldv < Q1_D || ldv % 8 || (bias && !dot) || (sigma && !vs)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(head_expand_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, v, ldv, R, E, bias, dot, sigma, vs);
-    return svla_launch_status();
+    return svla_launch<head_expand_kernel>(dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, v, ldv, R, E, bias, dot, sigma, vs);
 }
 extern "C" int svla_head_pick_bf16(const bf16_t* G, int R, const float* sigma, const float* bias, bf16_t* out, long ldo, void* stream) {
     if (!G || !out || R <= 0 || ldo < Q1_D || ldo % 8 || (sigma && !bias)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(head_pick_kernel, dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, G, R, sigma, bias, out, ldo);
-    return svla_launch_status();
+    return svla_launch<head_pick_kernel>(dim3((R + 3) / 4), dim3(256), 0, (hipStream_t)stream, G, R, sigma, bias, out, ldo);
 }

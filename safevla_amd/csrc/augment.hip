@@ -420,10 +420,9 @@ static bool aug_grouped_ok(int N, int H, int W, int group_len, const svla_aug_tr
     }
     return true;
 }
-// the table goes to the device scratch on the stream, in front of the launch that reads it (a pageable source is staged before hipMemcpyAsync returns)
+// the table goes to the device scratch on the stream, in front of the launch that reads it (a pageable source is staged before the copy call returns)
 static int aug_table_upload(const svla_aug_transform* th, svla_aug_transform* td, int G, hipStream_t s) {
-    HIP_CHECK_RET(hipMemcpyAsync(td, th, (size_t)G * sizeof(svla_aug_transform), hipMemcpyHostToDevice, s));
-    return SVLA_OK;
+    return svla_memcpy_async(td, th, (size_t)G * sizeof(svla_aug_transform), hipMemcpyHostToDevice, s);
 }
 
 // ---- C ABI ---------------------------------------------------------------------------------------------------------------------------
@@ -435,9 +434,8 @@ extern "C" int svla_aug_gray_partials(const unsigned char* x, int B, int H, int 
     const float f[4] = {f0, f1, f2, f3};
     if (!aug_single_jitter(nops, ops_packed, f, J, contrast_at)) return SVLA_EINVAL;
     const long img_bytes = (long)H * W * 3;
-    hipLaunchKernelGGL(aug_gray_partials_kernel, dim3(AUG_NPART, B), dim3(AUG_T), 0, (hipStream_t)stream, x, img_bytes, H * W, J, nops, partials, x,
+    return svla_launch<aug_gray_partials_kernel>(dim3(AUG_NPART, B), dim3(AUG_T), 0, (hipStream_t)stream, x, img_bytes, H * W, J, nops, partials, x,
                        x + (size_t)B * img_bytes);
-    return svla_launch_status();
 }
 
 extern "C" int svla_aug_jitter_blur_u8(const unsigned char* x, unsigned char* y, int B, int H, int W, int nops, int ops_packed, float f0, float f1, float f2,
@@ -450,17 +448,15 @@ extern "C" int svla_aug_jitter_blur_u8(const unsigned char* x, unsigned char* y,
     if (contrast_at >= 0 && !partials) return SVLA_EINVAL;
     AugBlur bl{};
     if (wx5) bl = AugBlur{1, wx5[0], wx5[1], wx5[2], wx5[3], wx5[4], wy9[0], wy9[1], wy9[2], wy9[3], wy9[4], wy9[5], wy9[6], wy9[7], wy9[8]};
-    hipLaunchKernelGGL(aug_jitter_blur_kernel, dim3(aug_tiles(H, W), B), dim3(AUG_T), 0, (hipStream_t)stream, x, y, H, W, J, partials, bl, x,
+    return svla_launch<aug_jitter_blur_kernel>(dim3(aug_tiles(H, W), B), dim3(AUG_T), 0, (hipStream_t)stream, x, y, H, W, J, partials, bl, x,
                        x + (size_t)B * H * W * 3);
-    return svla_launch_status();
 }
 
 extern "C" int svla_aug_resize_post_sharp_u8(const unsigned char* x, unsigned char* y, int B, int H, int W, int top, int left, int bh, int bw, int posterize,
                                              int sharpen, void* stream) {
     if (!x || !y || x == y || !aug_single_ok(B, H, W) || !aug_box_ok(H, W, top, left, bh, bw)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(aug_resize_post_sharp_kernel, dim3(aug_tiles(H, W), B), dim3(AUG_T), 0, (hipStream_t)stream, x, y, H, W, top, left, bh, bw,
+    return svla_launch<aug_resize_post_sharp_kernel>(dim3(aug_tiles(H, W), B), dim3(AUG_T), 0, (hipStream_t)stream, x, y, H, W, top, left, bh, bw,
                        posterize ? 1 : 0, sharpen ? 1 : 0, x, x + (size_t)B * H * W * 3);
-    return svla_launch_status();
 }
 
 extern "C" int svla_aug_gray_partials_grouped(const unsigned char* x, int N, int H, int W, int group_len, const svla_aug_transform* table_host,
@@ -469,9 +465,8 @@ extern "C" int svla_aug_gray_partials_grouped(const unsigned char* x, int N, int
     const int G = N / group_len;
     if (const int rc = aug_table_upload(table_host, table_dev, G, (hipStream_t)stream)) return rc;
     const long img_bytes = (long)H * W * 3;
-    hipLaunchKernelGGL(aug_gray_partials_grouped_kernel, dim3(AUG_NPART, group_len, G), dim3(AUG_T), 0, (hipStream_t)stream, x, img_bytes, H * W, table_dev, partials,
+    return svla_launch<aug_gray_partials_grouped_kernel>(dim3(AUG_NPART, group_len, G), dim3(AUG_T), 0, (hipStream_t)stream, x, img_bytes, H * W, table_dev, partials,
                        x, x + (size_t)N * img_bytes);
-    return svla_launch_status();
 }
 
 extern "C" int svla_aug_jitter_blur_grouped_u8(const unsigned char* x, unsigned char* y, int N, int H, int W, int group_len, const svla_aug_transform* table_host,
@@ -481,9 +476,8 @@ extern "C" int svla_aug_jitter_blur_grouped_u8(const unsigned char* x, unsigned 
     for (int g = 0; g < G; ++g)
         if (table_host[g].nops_before_contrast >= 0 && !partials) return SVLA_EINVAL;
     if (const int rc = aug_table_upload(table_host, table_dev, G, (hipStream_t)stream)) return rc;
-    hipLaunchKernelGGL(aug_jitter_blur_grouped_kernel, dim3(aug_tiles(H, W), group_len, G), dim3(AUG_T), 0, (hipStream_t)stream, x, y, H, W, table_dev, partials, x,
+    return svla_launch<aug_jitter_blur_grouped_kernel>(dim3(aug_tiles(H, W), group_len, G), dim3(AUG_T), 0, (hipStream_t)stream, x, y, H, W, table_dev, partials, x,
                        x + (size_t)N * H * W * 3);
-    return svla_launch_status();
 }
 
 extern "C" int svla_aug_resize_post_sharp_grouped_u8(const unsigned char* x, unsigned char* y, int N, int H, int W, int group_len,
@@ -491,7 +485,6 @@ extern "C" int svla_aug_resize_post_sharp_grouped_u8(const unsigned char* x, uns
     if (!x || !y || x == y || !aug_grouped_ok(N, H, W, group_len, table_host, table_dev)) return SVLA_EINVAL;
     const int G = N / group_len;
     if (const int rc = aug_table_upload(table_host, table_dev, G, (hipStream_t)stream)) return rc;
-    hipLaunchKernelGGL(aug_resize_post_sharp_grouped_kernel, dim3(aug_tiles(H, W), group_len, G), dim3(AUG_T), 0, (hipStream_t)stream, x, y, H, W, table_dev, x,
+    return svla_launch<aug_resize_post_sharp_grouped_kernel>(dim3(aug_tiles(H, W), group_len, G), dim3(AUG_T), 0, (hipStream_t)stream, x, y, H, W, table_dev, x,
                        x + (size_t)N * H * W * 3);
-    return svla_launch_status();
 }

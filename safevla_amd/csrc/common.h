@@ -2,10 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "launch.h"
-
-#define SVLA_OK 0
-#define SVLA_EINVAL (-1)
+#include "launch.h"      // (SVLA_OK / SVLA_EINVAL: launch_group.h)
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(4))) float f32x4;

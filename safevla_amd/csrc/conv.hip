@@ -236,10 +236,9 @@ extern "C" int svla_conv_nhwc_bf16(const bf16_t* x, const bf16_t* w, const float
     if (blocks >= (1ll << 31)) return SVLA_EINVAL;
     ConvArgs p{x, w, bias, residual, ldr, y, ldy, yG, yGS, (int)M, H, W, Cin, Cout, taps, epi};
     const dim3 grid((unsigned)blocks), block(CV_T);
-    if (BN == 128) hipLaunchKernelGGL(conv_igemm_bf16_kernel<128>, grid, block, 0, (hipStream_t)stream, p);
-    else if (BN == 64) hipLaunchKernelGGL(conv_igemm_bf16_kernel<64>, grid, block, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(conv_igemm_bf16_kernel<32>, grid, block, 0, (hipStream_t)stream, p);
-    return svla_launch_status();
+    if (BN == 128) return svla_launch<conv_igemm_bf16_kernel<128>>(grid, block, 0, (hipStream_t)stream, p);
+    if (BN == 64) return svla_launch<conv_igemm_bf16_kernel<64>>(grid, block, 0, (hipStream_t)stream, p);
+    return svla_launch<conv_igemm_bf16_kernel<32>>(grid, block, 0, (hipStream_t)stream, p);
 }
 
 extern "C" int svla_conv_stem_u8_bf16(const unsigned char* frames, int B, int H, int W, const float* mean3, const float* std3, const float* w, const float* bias,
@@ -252,15 +251,13 @@ extern "C" int svla_conv_stem_u8_bf16(const unsigned char* frames, int B, int H,
     if ((long long)B * H * W * 3 >= (1ll << 40) || (npix + CV_T - 1) / CV_T >= (1ll << 31)) return SVLA_EINVAL;
     float sc[3], of[3];
     for (int c = 0; c < 3; ++c) { sc[c] = 1.f / (255.f * std3[c]); of[c] = -mean3[c] / std3[c]; }
-    hipLaunchKernelGGL(conv_stem_u8_bf16_kernel, dim3((unsigned)((npix + CV_T - 1) / CV_T)), dim3(CV_T), 0, (hipStream_t)stream, frames, w, bias, y, (long)npix, H, W,
+    return svla_launch<conv_stem_u8_bf16_kernel>(dim3((unsigned)((npix + CV_T - 1) / CV_T)), dim3(CV_T), 0, (hipStream_t)stream, frames, w, bias, y, (long)npix, H, W,
                        OH, OW, sc[0], sc[1], sc[2], of[0], of[1], of[2]);
-    return svla_launch_status();
 }
 
 extern "C" int svla_avgpool2_nhwc_bf16(const bf16_t* x, int B, int H, int W, int C, bf16_t* y, void* stream) {
     if (!cv_aligned(x, 16) || !cv_aligned(y, 16) || B <= 0 || H < 2 || W < 2 || C <= 0 || (C % 8)) return SVLA_EINVAL;
     const long long n8 = (long long)B * (H / 2) * (W / 2) * (C / 8);
     if ((n8 + CV_T - 1) / CV_T >= (1ll << 31)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(avgpool2_nhwc_bf16_kernel, dim3((unsigned)((n8 + CV_T - 1) / CV_T)), dim3(CV_T), 0, (hipStream_t)stream, x, y, (long)n8, H, W, C / 8);
-    return svla_launch_status();
+    return svla_launch<avgpool2_nhwc_bf16_kernel>(dim3((unsigned)((n8 + CV_T - 1) / CV_T)), dim3(CV_T), 0, (hipStream_t)stream, x, y, (long)n8, H, W, C / 8);
 }

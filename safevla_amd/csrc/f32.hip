@@ -88,8 +88,7 @@ extern "C" int svla_gemm_f32(const float* A, long sam, long sak, const float* B,
                              int act, int accumulate, float alpha, const svla_dropout* drop, void* stream) {
     if (M <= 0 || N <= 0 || K <= 0 || act < 0 || act > 2 || !A || !B || !C) return SVLA_EINVAL;
     GemmF32Args p{A, sam, sak, B, sbn, sbk, bias, residual, ldr, mask, ldm, C, ldc, M, N, K, act, accumulate, alpha, drop_cfg(drop)};
-    hipLaunchKernelGGL(gemm_f32_kernel, dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
-    return svla_launch_status();
+    return svla_launch<gemm_f32_kernel>(dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 // out[n] += sum_m X[m*row_stride*ldx + n]  (bias gradients), one block per 64 columns, rows strided over the block's 4 waves
@@ -108,8 +107,7 @@ __global__ void colsum_f32_kernel(const float* __restrict__ X, long ldx, int M, 
 extern "C" int svla_colsum_f32(const float* X, long ldx, int M, int N, int row_stride, float* out, void* stream) {
     if (M <= 0 || N <= 0) return SVLA_EINVAL;
     int gy = (M + 255) / 256; if (gy > 256) gy = 256;
-    hipLaunchKernelGGL(colsum_f32_kernel, dim3((N + 63) / 64, gy), dim3(256), 0, (hipStream_t)stream, X, ldx, M, N, row_stride > 0 ? row_stride : 1, out);
-    return svla_launch_status();
+    return svla_launch<colsum_f32_kernel>(dim3((N + 63) / 64, gy), dim3(256), 0, (hipStream_t)stream, X, ldx, M, N, row_stride > 0 ? row_stride : 1, out);
 }
 
 // ================================================================================================ attention (fp32)
@@ -347,15 +345,13 @@ extern "C" int svla_attn_fwd_f32(const float* Q, const float* K, const float* V,
         if (rows <= 0 || S > AF_DEC_MAXS || H <= 0 || head_dim != 64 || Sq != 1 || bias || mask_mode != 0 || drop_cfg(drop).thr || (kv_rows && kv_rows < S)) return SVLA_EINVAL;
         AttnF32Args pd{Q, K, V, ld, O, ldo, LSE, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, kvalid, S, H, 0, scale,
                        kv_rows ? kv_rows : S, 1, ldq, 0, drop_cfg(nullptr), 64};
-        hipLaunchKernelGGL(attn_decode_f32_kernel, dim3(rows * H), dim3(256), 0, (hipStream_t)stream, pd);
-        return svla_launch_status();
+        return svla_launch<attn_decode_f32_kernel>(dim3(rows * H), dim3(256), 0, (hipStream_t)stream, pd);
     }
     if (rows <= 0 || S <= 0 || S > AF_MAXS || H <= 0 || head_dim <= 0 || head_dim > AF_MAXHD || (mask_mode == 1 && !traj) || Sq < 0 || Sq > S) return SVLA_EINVAL;
     if (kv_rows && kv_rows < S) return SVLA_EINVAL;
     AttnF32Args p{Q, K, V, ld, O, ldo, LSE, nullptr, 0, nullptr, nullptr, nullptr, 0, traj, bias, kvalid, S, H, mask_mode, scale,
                   kv_rows ? kv_rows : S, Sq ? Sq : S, Sq ? ldq : ld, 0, drop_cfg(drop), head_dim};
-    hipLaunchKernelGGL(attn_fwd_f32_kernel, dim3(rows * H), dim3(256), 0, (hipStream_t)stream, p);
-    return svla_launch_status();
+    return svla_launch<attn_fwd_f32_kernel>(dim3(rows * H), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 extern "C" int svla_attn_bwd_f32(const float* Q, const float* K, const float* V, long ld, const float* O, long ldo, const float* LSE,
@@ -365,8 +361,7 @@ extern "C" int svla_attn_bwd_f32(const float* Q, const float* K, const float* V,
     if (rows <= 0 || S <= 0 || S > AF_MAXS || H <= 0 || head_dim <= 0 || head_dim > AF_MAXHD || (mask_mode == 1 && !traj) || Sq < 0 || Sq > S || !LSE) return SVLA_EINVAL;
     AttnF32Args p{Q, K, V, ld, const_cast<float*>(O), ldo, const_cast<float*>(LSE), dO, lddo, dQ, dK, dV, ldd, traj, nullptr, kvalid, S, H,
                   mask_mode, scale, S, Sq ? Sq : S, Sq ? ldq : ld, Sq ? lddq : ldd, drop_cfg(drop), head_dim};
-    hipLaunchKernelGGL(attn_bwd_f32_kernel, dim3(rows * H), dim3(256), 0, (hipStream_t)stream, p);
-    return svla_launch_status();
+    return svla_launch<attn_bwd_f32_kernel>(dim3(rows * H), dim3(256), 0, (hipStream_t)stream, p);
 }
 
 // ================================================================================================ glue (fp32 twins of misc.hip)
@@ -382,8 +377,7 @@ __global__ void feat_to_tokens_f32_kernel(const float* __restrict__ feat, int R,
 extern "C" int svla_feat_to_tokens_f32(const float* feat, int R, int C, int P, int cam, int ncam, float* out, void* stream) {
     if (R <= 0 || C <= 0 || P <= 0 || cam >= ncam) return SVLA_EINVAL;
     long blocks = ((long)R * C * P + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(feat_to_tokens_f32_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, feat, R, C, P, cam, ncam, out);
-    return svla_launch_status();
+    return svla_launch<feat_to_tokens_f32_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, feat, R, C, P, cam, ncam, out);
 }
 
 __global__ void fusion_fill_f32_kernel(const float* __restrict__ fusion_token, const float* __restrict__ text, const int* __restrict__ gid,
@@ -399,8 +393,7 @@ __global__ void fusion_fill_f32_kernel(const float* __restrict__ fusion_token, c
 extern "C" int svla_fusion_fill_f32(const float* fusion_token, const float* text, const int* gid, int R, int S, int L, int text_off,
                                     int D, float* x0, void* stream) {
     if (R <= 0 || text_off + L > S || D <= 0) return SVLA_EINVAL;
-    hipLaunchKernelGGL(fusion_fill_f32_kernel, dim3(R), dim3(256), 0, (hipStream_t)stream, fusion_token, text, gid, R, S, L, text_off, D, x0);
-    return svla_launch_status();
+    return svla_launch<fusion_fill_f32_kernel>(dim3(R), dim3(256), 0, (hipStream_t)stream, fusion_token, text, gid, R, S, L, text_off, D, x0);
 }
 
 __global__ void fusion_text_bwd_f32_kernel(const float* __restrict__ dx0, const int* __restrict__ gid, int T, int B, int S, int L,
@@ -419,8 +412,7 @@ __global__ void fusion_text_bwd_f32_kernel(const float* __restrict__ dx0, const 
 }
 extern "C" int svla_fusion_text_bwd_f32(const float* dx0, const int* gid, int T, int B, int S, int L, int text_off, int D, float* dtext, void* stream) {
     if (T <= 0 || B <= 0 || L <= 0 || D <= 0) return SVLA_EINVAL;
-    hipLaunchKernelGGL(fusion_text_bwd_f32_kernel, dim3(B, L), dim3(256), 0, (hipStream_t)stream, dx0, gid, T, B, S, L, text_off, D, dtext);
-    return svla_launch_status();
+    return svla_launch<fusion_text_bwd_f32_kernel>(dim3(B, L), dim3(256), 0, (hipStream_t)stream, dx0, gid, T, B, S, L, text_off, D, dtext);
 }
 
 __global__ void decoder_embed_f32_kernel(const float* __restrict__ xf, long xf_row_stride, const float* __restrict__ act_tab,
@@ -450,9 +442,8 @@ extern "C" int svla_decoder_embed_fwd_f32(const float* xf, long xf_row_stride, c
     if (T <= 0 || B <= 0 || D <= 0) return SVLA_EINVAL;
     if ((hand_tab == nullptr) != (hand == nullptr)) return SVLA_EINVAL;
     if ((act_tab == nullptr) != (prev_actions == nullptr) || (act_tab == nullptr) != (masks == nullptr)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(decoder_embed_f32_kernel, dim3(T * B), dim3(256), 0, (hipStream_t)stream, xf, xf_row_stride, act_tab, hand_tab, div_term,
+    return svla_launch<decoder_embed_f32_kernel>(dim3(T * B), dim3(256), 0, (hipStream_t)stream, xf, xf_row_stride, act_tab, hand_tab, div_term,
                        prev_actions, masks, hand, time_step, T, B, n_actions, D, out);
-    return svla_launch_status();
 }
 
 __global__ void decoder_embed_bwd_f32_kernel(const float* __restrict__ dout, const int64_t* __restrict__ prev_actions,
@@ -476,9 +467,8 @@ extern "C" int svla_decoder_embed_bwd_f32(const float* dout, const int64_t* prev
     if (T <= 0 || B <= 0 || D <= 0) return SVLA_EINVAL;
     if ((d_hand_tab == nullptr) != (hand == nullptr)) return SVLA_EINVAL;
     if ((d_act_tab == nullptr) != (prev_actions == nullptr) || (d_act_tab == nullptr) != (masks == nullptr)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(decoder_embed_bwd_f32_kernel, dim3(T * B), dim3(256), 0, (hipStream_t)stream, dout, prev_actions, masks, hand, T, B,
+    return svla_launch<decoder_embed_bwd_f32_kernel>(dim3(T * B), dim3(256), 0, (hipStream_t)stream, dout, prev_actions, masks, hand, T, B,
                        n_actions, D, dxf, dxf_row_stride, d_act_tab, d_hand_tab);
-    return svla_launch_status();
 }
 
 __global__ void rows_add_f32_kernel(float* __restrict__ dst, long dst_ld, const float* __restrict__ src, long src_ld, int rows, int D) {
@@ -489,8 +479,7 @@ __global__ void rows_add_f32_kernel(float* __restrict__ dst, long dst_ld, const 
 extern "C" int svla_rows_add_f32(float* dst, long dst_ld, const float* src, long src_ld, int rows, int D, void* stream) {
     if (rows <= 0 || D <= 0) return SVLA_EINVAL;
     long blocks = ((long)rows * D + 255) / 256; if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(rows_add_f32_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dst, dst_ld, src, src_ld, rows, D);
-    return svla_launch_status();
+    return svla_launch<rows_add_f32_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, dst, dst_ld, src, src_ld, rows, D);
 }
 
 __global__ void swiglu_fwd_f32_kernel(const float* __restrict__ ab, long M, int Hd, float* __restrict__ g) {
@@ -514,14 +503,12 @@ __global__ void swiglu_bwd_f32_kernel(const float* __restrict__ ab, const float*
 extern "C" int svla_swiglu_fwd_f32(const float* ab, long M, int Hd, float* g, void* stream) {
     if (M <= 0 || Hd <= 0) return SVLA_EINVAL;
     long blocks = (M * Hd + 255) / 256; if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(swiglu_fwd_f32_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ab, M, Hd, g);
-    return svla_launch_status();
+    return svla_launch<swiglu_fwd_f32_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ab, M, Hd, g);
 }
 extern "C" int svla_swiglu_bwd_f32(const float* ab, const float* dg, long M, int Hd, float* dab, void* stream) {
     if (M <= 0 || Hd <= 0) return SVLA_EINVAL;
     long blocks = (M * Hd + 255) / 256; if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(swiglu_bwd_f32_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ab, dg, M, Hd, dab);
-    return svla_launch_status();
+    return svla_launch<swiglu_bwd_f32_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ab, dg, M, Hd, dab);
 }
 
 __global__ void embed_gather_f32_kernel(const float* __restrict__ table, const int64_t* __restrict__ ids, long n, int D, float* __restrict__ out) {
@@ -532,8 +519,7 @@ __global__ void embed_gather_f32_kernel(const float* __restrict__ table, const i
 extern "C" int svla_embed_gather_f32(const float* table, const int64_t* ids, long n, int D, float* out, void* stream) {
     if (n <= 0 || D <= 0) return SVLA_EINVAL;
     long blocks = (n * D + 255) / 256; if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(embed_gather_f32_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, table, ids, n, D, out);
-    return svla_launch_status();
+    return svla_launch<embed_gather_f32_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, table, ids, n, D, out);
 }
 
 __global__ void dropout_f32_kernel(float* __restrict__ x, long rows, int N, DropCfg drop) {
@@ -550,6 +536,5 @@ extern "C" int svla_dropout_f32(float* x, long rows, int N, const svla_dropout* 
     const DropCfg c = drop_cfg(drop);
     if (!c.thr) return SVLA_OK;
     long blocks = (rows * N / 4 + 255) / 256; if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(dropout_f32_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, rows, N, c);
-    return svla_launch_status();
+    return svla_launch<dropout_f32_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, rows, N, c);
 }

@@ -1571,8 +1571,9 @@ extern "C" int svla_colsum_bf16(const bf16_t* dY, long ldy, int M, int N, int ro
         const int rpp = threads / (n / 8);
         int blocks = (M + rpp - 1) / rpp;
         if (blocks > 1024) blocks = 1024;
-        hipLaunchKernelGGL(colsum_bf16_kernel, dim3(blocks), dim3(threads), threads * 8 * sizeof(float), (hipStream_t)stream, dY + c0, ldy,
-                           M, n, row_stride > 0 ? row_stride : 1, db + c0, g_svla_det);
+        if (const int rc = svla_launch<colsum_bf16_kernel>(dim3(blocks), dim3(threads), threads * 8 * sizeof(float), (hipStream_t)stream, dY + c0, ldy, M, n,
+                                                           row_stride > 0 ? row_stride : 1, db + c0, g_svla_det))
+            return rc;
     }
-    return svla_launch_status();
+    return SVLA_OK;
 }

@@ -1,12 +1,17 @@
-// Tower-grouped launches (round 6).
+// Tower-grouped launches (round 6) and THE launch path of csrc/: every kernel launch, memset and copy of the library goes through this file.
 //
 // The three towers of the actor-critic (actor, reward critic, cost critic: separate_actor_critic.py:27-37) execute the SAME kernel
 // sequence on the same shapes with different weights.  At an acting step every one of those kernels is small (64 ... 11 584 rows): three
 // streams of ~100 dependent launches each, where a chip-filling kernel of one tower holds up the other two (profiles/r05_policy_step_kernel_stats.txt).
-// With a capture open (svla_group_begin), a launch site that goes through SVLA_LAUNCH does not launch: it stores the kernel's arguments.
+// With a capture open (svla_group_begin), a launch site that goes through SVLA_LAUNCH / SVLA_LAUNCH_TWIN does not launch: it stores the kernel's arguments.
 // svla_group_end then issues, for launch j of the call, ONE grid whose blockIdx.z selects the member's argument block -- three times the
 // workgroups per dispatch, one dependency chain instead of three.  Anything that is not identical across the members (kernel, grid, block,
 // LDS bytes) falls back to one launch per member, in member order, on the same stream: always correct, only slower.
+//
+// What a capture decides is host logic without HIP, in launch_group.h (the rules are written out there): a member's launches keep the order of its calls --
+// svla_launch, svla_asm_launch2, svla_memset_async and svla_memcpy_async issue the member's pending launches before their own, as does a deferral into a full queue --
+// and a capture has ONE stream, that of its first launch; a site or an end that names another is SVLA_EINVAL.  This file is the HIP side: the opt-in for dynamic
+// LDS, the launchers and the grouped twin.
 //
 // A kernel takes part by being written as  __device__ body(args...)  +  __global__ kernel(args...) { body(args...); }  (the single-launch kernel keeps
 // its name, signature and code); its grouped twin is svla_grouped<&body, ...>, generated here.
@@ -16,10 +21,7 @@
 #include <atomic>
 #include <mutex>
 #include <utility>
-
-#define SVLA_MAXG 3             // towers
-#define SVLA_MAXQ 8             // launches one member may defer in one capture (svla_group_begin ... svla_group_end)
-#define SVLA_DEFER_ARG_BYTES 512
+#include "launch_group.h"
 
 template <typename... Ts> struct ArgPack;
 template <> struct ArgPack<> {};
@@ -46,26 +48,12 @@ __global__ void __launch_bounds__(MAXT, MINB) svla_grouped(GroupedArgs<ArgPack<T
     svla_call_body<Body, Ts...>(g.a[blockIdx.z], std::index_sequence_for<Ts...>{});
 }
 
-struct DeferredLaunch {
-    // issues members m[0..n): grouped when n > 1 (the caller has checked that they are identical in everything but the arguments)
-    int (*flush)(const DeferredLaunch* const* m, int n, hipStream_t s);
-    dim3 grid, block;
-    unsigned smem;
-    hipStream_t stream;
-    alignas(16) unsigned char args[SVLA_DEFER_ARG_BYTES];
-};
-struct GroupCapture {
-    int size = 0, member = 0;
-    int n[SVLA_MAXG] = {0, 0, 0};
-    DeferredLaunch q[SVLA_MAXG][SVLA_MAXQ];
-    int overflow = 0;
-    long grouped = 0, single = 0;      // statistics since svla_group_stats was last read
-};
 GroupCapture* svla_group_capture();    // misc.hip: this thread's open capture, or nullptr
 int svla_group_size();                 // members of the open capture (1: none) -- dispatchers size persistent grids / choose kernels for the GROUP's work
 int svla_cu_count();                   // misc.hip: compute units of the current device, cached (0: the query failed); never refuses inside a stream capture
 
 static inline int svla_launch_status() { return (int)hipGetLastError(); }
+static inline dim3 svla_dim3(LaunchDim d) { return dim3(d.x, d.y, d.z); }
 
 // Dynamic LDS beyond 64 KiB has to be asked for, per kernel: raises Kern's limit when `bytes` exceeds what this process has already cleared for it (a high-water
 // mark that starts at 0: sizes below the default limit are asked for too, once, rather than trusting where exactly that default lies).  THE one place that
@@ -82,32 +70,58 @@ template <auto Kern> inline int svla_lds_optin(size_t bytes) {
     cleared.store((unsigned)bytes, std::memory_order_release);
     return 0;
 }
-// A kernel without a grouped twin: opt in when needed, launch, report.  (Kern may be a template-id with commas: this is a function template, not a macro.)
-template <auto Kern, typename... As> inline int svla_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const As&... a) {
+// opt in when needed, launch, report: what a flush function and svla_launch end in.  Asks no capture.
+template <auto Kern, typename... As> inline int svla_issue(dim3 grid, dim3 block, size_t lds, hipStream_t s, const As&... a) {
     if (const int rc = svla_lds_optin<Kern>(lds)) return rc;
     hipLaunchKernelGGL(Kern, grid, block, lds, s, a...);
     return svla_launch_status();
 }
+// Whatever is issued at once -- a kernel without a grouped twin, an assembly kernel, a memset, a copy -- asks the thread's open capture first (launch_group.h:
+// group_direct): the member's pending launches go ahead of it, and another stream than the capture's is refused.  One thread-local read when none is open.
+inline int svla_direct(hipStream_t s) {
+    GroupCapture* gc = svla_group_capture();
+    return gc ? group_direct(*gc, (void*)s) : 0;
+}
+// THE launch of a kernel without a grouped twin.  (Kern may be a template-id with commas: this is a function template, not a macro.)
+template <auto Kern, typename... As> inline int svla_launch(dim3 grid, dim3 block, size_t lds, hipStream_t s, const As&... a) {
+    if (const int rc = svla_direct(s)) return rc;
+    return svla_issue<Kern>(grid, block, lds, s, a...);
+}
+inline int svla_memset_async(void* p, int value, size_t bytes, hipStream_t s) {
+    if (const int rc = svla_direct(s)) return rc;
+    return (int)hipMemsetAsync(p, value, bytes, s);
+}
+inline int svla_memcpy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+    if (const int rc = svla_direct(s)) return rc;
+    return (int)hipMemcpyAsync(dst, src, bytes, kind, s);
+}
 
 // issue n >= 1 members' argument blocks as ONE grid of the grouped twin (grid.z = n)
 template <auto Body, int MAXT, int MINB, typename... Ts>
-inline int svla_twin_launch(const DeferredLaunch* const* m, int n, hipStream_t s) {
+inline int svla_twin_launch(const DeferredLaunch* const* m, int n, void* s) {
     using Pack = ArgPack<Ts...>;
     GroupedArgs<Pack> g;
     for (int i = 0; i < SVLA_MAXG; ++i) memcpy((void*)&g.a[i], m[i < n ? i : 0]->args, sizeof(Pack));
     if (const int rc = svla_lds_optin<svla_grouped<Body, MAXT, MINB, Ts...>>(m[0]->smem)) return rc;      // the twin is a kernel of its own: cleared apart from the single-launch kernel
-    dim3 grid = m[0]->grid;
+    dim3 grid = svla_dim3(m[0]->grid);
     grid.z = (unsigned)n;
-    hipLaunchKernelGGL((svla_grouped<Body, MAXT, MINB, Ts...>), grid, m[0]->block, m[0]->smem, s, g);
-    return (int)hipGetLastError();
+    hipLaunchKernelGGL((svla_grouped<Body, MAXT, MINB, Ts...>), grid, svla_dim3(m[0]->block), m[0]->smem, (hipStream_t)s, g);
+    return svla_launch_status();
 }
-template <typename... Ts> inline void svla_defer_fill(DeferredLaunch& d, int (*flush)(const DeferredLaunch* const*, int, hipStream_t), dim3 grid, dim3 block, size_t smem,
-                                                      hipStream_t s, const Ts&... a) {
+// A deferral site: inside a capture the launch is stored in the member's queue (0, or why it was refused), outside it is issued through the same flush as a
+// group of one.  `flush` is all that tells a kernel with a single-launch form from one without.
+typedef int (*SvlaFlush)(const DeferredLaunch* const*, int, void*);
+template <typename... Ts> inline int svla_defer_or_issue(SvlaFlush flush, dim3 grid, dim3 block, size_t smem, hipStream_t s, const Ts&... a) {
     static_assert(sizeof(ArgPack<Ts...>) <= SVLA_DEFER_ARG_BYTES, "deferred argument block too small");
-    d.flush = flush;
-    d.grid = grid; d.block = block; d.smem = (unsigned)smem; d.stream = s;
+    GroupCapture* gc = svla_group_capture();
+    DeferredLaunch now, *d = &now;
+    int rc = 0;
+    if (gc && !(d = group_defer(*gc, (void*)s, &rc))) return rc;
+    d->flush = flush;
+    d->grid = LaunchDim{grid.x, grid.y, grid.z}; d->block = LaunchDim{block.x, block.y, block.z}; d->smem = (unsigned)smem;
     const ArgPack<Ts...> p = pack_make<Ts...>(a...);
-    memcpy(d.args, (const void*)&p, sizeof(p));
+    memcpy(d->args, (const void*)&p, sizeof(p));
+    return gc ? 0 : flush(&d, 1, (void*)s);
 }
 
 // A kernel with a same-named single-launch __global__ (Kern) and a grouped twin generated from its body
@@ -116,26 +130,16 @@ template <typename... Ts, void (*Kern)(Ts...), void (*Body)(Ts...), int MAXT, in
 struct Launch<Kern, Body, MAXT, MINB> {
     using Pack = ArgPack<Ts...>;
     template <size_t... I>
-    static int single(const DeferredLaunch& d, hipStream_t s, std::index_sequence<I...>) {
+    static int single(const DeferredLaunch& d, void* s, std::index_sequence<I...>) {
         Pack p;
         memcpy((void*)&p, d.args, sizeof(Pack));
-        return svla_launch<Kern>(d.grid, d.block, d.smem, s, pack_get<I>(p)...);
+        return svla_issue<Kern>(svla_dim3(d.grid), svla_dim3(d.block), d.smem, (hipStream_t)s, pack_get<I>(p)...);
     }
-    static int flush(const DeferredLaunch* const* m, int n, hipStream_t s) {
+    static int flush(const DeferredLaunch* const* m, int n, void* s) {
         if (n == 1) return single(*m[0], s, std::index_sequence_for<Ts...>{});
         return svla_twin_launch<Body, MAXT, MINB, Ts...>(m, n, s);
     }
-    // 0 when the launch was deferred, else its status
-    static int go(dim3 grid, dim3 block, size_t smem, hipStream_t s, Ts... a) {
-        GroupCapture* gc = svla_group_capture();
-        if (!gc || gc->n[gc->member] >= SVLA_MAXQ) {      // (no member defers SVLA_MAXQ launches in a capture; if one ever does, the launch is issued at once and the capture is marked)
-            if (gc) gc->overflow = 1;
-            return svla_launch<Kern>(grid, block, smem, s, a...);
-        }
-        svla_defer_fill<Ts...>(gc->q[gc->member][gc->n[gc->member]], &flush, grid, block, smem, s, a...);
-        gc->n[gc->member] += 1;
-        return 0;
-    }
+    static int go(dim3 grid, dim3 block, size_t smem, hipStream_t s, Ts... a) { return svla_defer_or_issue<Ts...>(&flush, grid, block, smem, s, a...); }
 };
 // A kernel that exists ONLY as the grouped form: a single launch is a group of one (grid.z = 1).  For the attention forward kernels: their bodies inlined into a
 // plain same-named __global__ compiled worse than the original kernels did (attn_fwd_persist_kernel<12>: 109 spilled VGPRs against 6, 2.99 -> 5.97 ms per launch
@@ -143,20 +147,8 @@ struct Launch<Kern, Body, MAXT, MINB> {
 template <auto Body, int MAXT, int MINB> struct LaunchTwin;
 template <typename... Ts, void (*Body)(Ts...), int MAXT, int MINB>
 struct LaunchTwin<Body, MAXT, MINB> {
-    static int flush(const DeferredLaunch* const* m, int n, hipStream_t s) { return svla_twin_launch<Body, MAXT, MINB, Ts...>(m, n, s); }
-    static int go(dim3 grid, dim3 block, size_t smem, hipStream_t s, Ts... a) {
-        GroupCapture* gc = svla_group_capture();
-        if (!gc || gc->n[gc->member] >= SVLA_MAXQ) {
-            if (gc) gc->overflow = 1;
-            DeferredLaunch d;
-            svla_defer_fill<Ts...>(d, &flush, grid, block, smem, s, a...);
-            const DeferredLaunch* one = &d;
-            return flush(&one, 1, s);
-        }
-        svla_defer_fill<Ts...>(gc->q[gc->member][gc->n[gc->member]], &flush, grid, block, smem, s, a...);
-        gc->n[gc->member] += 1;
-        return 0;
-    }
+    static int flush(const DeferredLaunch* const* m, int n, void* s) { return svla_twin_launch<Body, MAXT, MINB, Ts...>(m, n, s); }
+    static int go(dim3 grid, dim3 block, size_t smem, hipStream_t s, Ts... a) { return svla_defer_or_issue<Ts...>(&flush, grid, block, smem, s, a...); }
 };
 // kern / body may be template-ids with commas: pass them in parentheses
 #define SVLA_LAUNCH(kern, body, maxt, minb, grid, block, smem, stream, ...) \

@@ -27,8 +27,7 @@ __global__ void feat_to_tokens_kernel(const float* __restrict__ feat, int R, int
 
 extern "C" int svla_feat_to_tokens(const float* feat, int R, int C, int P, int cam, int ncam, bf16_t* out, void* stream) {
     if (R <= 0 || (C % 64) || P > 85 || cam >= ncam) return SVLA_EINVAL;
-    hipLaunchKernelGGL(feat_to_tokens_kernel, dim3(R, C / 64), dim3(256), 0, (hipStream_t)stream, feat, R, C, P, cam, ncam, out);
-    return svla_launch_status();
+    return svla_launch<feat_to_tokens_kernel>(dim3(R, C / 64), dim3(256), 0, (hipStream_t)stream, feat, R, C, P, cam, ncam, out);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -86,8 +85,7 @@ __global__ void fusion_text_bwd_kernel(const bf16_t* __restrict__ dx0, const int
 extern "C" int svla_fusion_text_bwd(const bf16_t* dx0, const int* gid, int T, int B, int S, int L, int text_off, int D, float* dtext,
                                     void* stream) {
     if (T <= 0 || B <= 0 || L <= 0 || D <= 0 || (D % 8)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(fusion_text_bwd_kernel, dim3(B, L, (D + 511) / 512), dim3(64), 0, (hipStream_t)stream, dx0, gid, T, B, S, L, text_off, D, dtext, g_svla_det);
-    return svla_launch_status();
+    return svla_launch<fusion_text_bwd_kernel>(dim3(B, L, (D + 511) / 512), dim3(64), 0, (hipStream_t)stream, dx0, gid, T, B, S, L, text_off, D, dtext, g_svla_det);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -272,8 +270,7 @@ extern "C" int svla_det_finalize(float* f32, long long* i64_shadow, long n, void
     if (n <= 0 || !f32 || !i64_shadow) return SVLA_EINVAL;
     long blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(det_finalize_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, f32, i64_shadow, n, g_svla_det.unscale);
-    return svla_launch_status();
+    return svla_launch<det_finalize_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, f32, i64_shadow, n, g_svla_det.unscale);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -327,8 +324,7 @@ extern "C" int svla_swiglu_fwd(const bf16_t* ab, long M, int Hd, bf16_t* g, void
 extern "C" int svla_swiglu_bwd(const bf16_t* ab, const bf16_t* dg, long M, int Hd, bf16_t* dab, void* stream) {
     if (M <= 0 || (Hd % 8)) return SVLA_EINVAL;
     long blocks = (M * (Hd / 8) + 255) / 256; if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(swiglu_bwd_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ab, dg, M, Hd, dab);
-    return svla_launch_status();
+    return svla_launch<swiglu_bwd_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, ab, dg, M, Hd, dab);
 }
 
 // ------------------------------------------------------------------------------------------------ optimiser
@@ -387,9 +383,8 @@ extern "C" int svla_sumsq_f32(const float* g, long n, double* out, void* stream)
             g_sumsq_slots[g_sumsq_n++] = SumsqSlot{dev, (hipStream_t)stream, scratch};
         }
     }
-    HIP_CHECK_RET(hipMemsetAsync(scratch + 1024, 0, sizeof(double), (hipStream_t)stream));
-    hipLaunchKernelGGL(sumsq_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, g, n, out, scratch, (unsigned*)(scratch + 1024));
-    return svla_launch_status();
+    if (const int rc = svla_memset_async(scratch + 1024, 0, sizeof(double), (hipStream_t)stream)) return rc;
+    return svla_launch<sumsq_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, g, n, out, scratch, (unsigned*)(scratch + 1024));
 }
 
 // torch.optim.Adam (amsgrad=False) / AdamW (decoupled ``weight_decay``: p *= 1 - lr*wd first) fused with clip_grad_norm_: the clip coefficient is read
@@ -421,9 +416,8 @@ extern "C" int svla_adam_step_f32(float* p, const float* g, float* m, float* v, 
     const float bc1 = 1.f - powf(beta1, (float)step);
     const float bc2s = sqrtf(1.f - powf(beta2, (float)step));
     long blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(adam_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps,
+    return svla_launch<adam_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps,
                        bc1, bc2s, gnorm_sq, max_norm, grad_scale, 1.f - lr * weight_decay);
-    return svla_launch_status();
 }
 
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ s, bf16_t* __restrict__ d, long n) {
@@ -432,8 +426,7 @@ __global__ void cast_f32_bf16_kernel(const float* __restrict__ s, bf16_t* __rest
 extern "C" int svla_cast_f32_bf16(const float* src, bf16_t* dst, long n, void* stream) {
     if (n <= 0) return SVLA_EINVAL;
     long blocks = (n + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, src, dst, n);
-    return svla_launch_status();
+    return svla_launch<cast_f32_bf16_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, src, dst, n);
 }
 
 // dst[c, r] (bf16) = src[r, c] (f32): transposed bf16 weight copies for the input-gradient GEMMs
@@ -449,9 +442,8 @@ __global__ void transpose_cast_kernel(const float* __restrict__ s, int rows, int
 }
 extern "C" int svla_transpose_cast_f32_bf16(const float* src, int rows, int cols, bf16_t* dst, void* stream) {
     if (rows <= 0 || cols <= 0) return SVLA_EINVAL;
-    hipLaunchKernelGGL(transpose_cast_kernel, dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, (hipStream_t)stream, src, rows,
+    return svla_launch<transpose_cast_kernel>(dim3((cols + 31) / 32, (rows + 31) / 32), dim3(256), 0, (hipStream_t)stream, src, rows,
                        cols, dst);
-    return svla_launch_status();
 }
 
 // rows of a table -> bf16 rows (T5 shared embedding gather): out[i, :] = table[ids[i], :]
@@ -494,8 +486,7 @@ __global__ void row_hash_kernel(const unsigned char* __restrict__ rows, long n_r
 }
 extern "C" int svla_row_hash_u8(const unsigned char* rows, long n_rows, int row_bytes, int64_t* out, void* stream) {
     if (n_rows <= 0 || row_bytes <= 0) return SVLA_EINVAL;
-    hipLaunchKernelGGL(row_hash_kernel, dim3((int)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows, n_rows, row_bytes, out);
-    return svla_launch_status();
+    return svla_launch<row_hash_kernel>(dim3((int)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, rows, n_rows, row_bytes, out);
 }
 
 // dst[r, :] += src[r, :] for D-wide bf16 rows with independent row strides (token-0 rows of a [R, S, D] gradient)
@@ -512,8 +503,7 @@ __global__ void rows_add_kernel(bf16_t* __restrict__ dst, long dst_ld, const bf1
 }
 extern "C" int svla_rows_add_bf16(bf16_t* dst, long dst_ld, const bf16_t* src, long src_ld, int rows, int D, void* stream) {
     if (rows <= 0 || D <= 0 || (D % 8) || (dst_ld % 8) || (src_ld % 8)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(rows_add_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dst, dst_ld, src, src_ld, rows, D);
-    return svla_launch_status();
+    return svla_launch<rows_add_kernel>(dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, dst, dst_ld, src, src_ld, rows, D);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -591,9 +581,8 @@ extern "C" int svla_patchify_u8_bf16(const unsigned char* frames, int B, int H, 
     const size_t lds = (((size_t)P * pitch + 15) & ~(size_t)15) + (size_t)KP * 3;
     // aligned word loads may touch up to 3 bytes on either side of a row segment: inside the frame buffer unless the crop ends at the very last byte of it
     const int wide = ((uintptr_t)frames % 4 == 0) && (crop_x > 0 || ((size_t)W * 3) % 4 == 0) && ((size_t)(crop_x + gw * P) * 3 + 3 <= (size_t)W * 3 || gh * P < H) ? 1 : 0;
-    hipLaunchKernelGGL(patchify_u8_kernel, dim3(B * gh), dim3(256), lds, (hipStream_t)stream, frames, H, W, crop_x, P, gh, gw, KP,
+    return svla_launch<patchify_u8_kernel>(dim3(B * gh), dim3(256), lds, (hipStream_t)stream, frames, H, W, crop_x, P, gh, gw, KP,
                        mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], out, wide);
-    return svla_launch_status();
 }
 
 // DataAugmentationPreprocessor.process without augmentation (dino_preprocessors.py:224-239): u8 HWC -> (x/255 - mean)/std fp32 HWC
@@ -622,9 +611,8 @@ __global__ void normalize_u8_kernel(const unsigned char* __restrict__ x, long n,
 extern "C" int svla_normalize_u8_f32(const unsigned char* x, long n, const float* mean3, const float* std3, float* y, void* stream) {
     if (n <= 0 || (n % 3) || ((uintptr_t)x % 4) || ((uintptr_t)y % 16)) return SVLA_EINVAL;
     long blocks = ((n >> 2) + 255) / 256; if (blocks > 8192) blocks = 8192; if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(normalize_u8_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, n, mean3[0], mean3[1], mean3[2],
+    return svla_launch<normalize_u8_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, x, n, mean3[0], mean3[1], mean3[2],
                        std3[0], std3[1], std3[2], y);
-    return svla_launch_status();
 }
 
 // x_norm_patchtokens [B, skip + gh*gw, C] (bf16) -> AdaptiveAvgPool2d((oh, ow)) over the gh x gw patch grid
@@ -649,9 +637,8 @@ __global__ void adaptive_pool_kernel(const bf16_t* __restrict__ x, int skip, int
 extern "C" int svla_adaptive_pool_tokens(const bf16_t* x, int B, int skip, int gh, int gw, int C, int oh, int ow, int cam, int ncam,
                                          bf16_t* tok_out, float* chw_out, void* stream) {
     if (B <= 0 || cam >= ncam || (!tok_out && !chw_out)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(adaptive_pool_kernel, dim3(B * oh * ow), dim3(128), 0, (hipStream_t)stream, x, skip, gh, gw, C, oh, ow, cam, ncam,
+    return svla_launch<adaptive_pool_kernel>(dim3(B * oh * ow), dim3(128), 0, (hipStream_t)stream, x, skip, gh, gw, C, oh, ow, cam, ncam,
                        tok_out, chw_out);
-    return svla_launch_status();
 }
 
 // y[b, 0, :] = cls + pos[0]; y[b, 1 + p, :] = patch[b, p, :] + pos[1 + p]   (DINOv2 prepare_tokens: cls token + position embedding)
@@ -674,8 +661,7 @@ __global__ void vit_tokens_kernel(const bf16_t* __restrict__ patch, const float*
 extern "C" int svla_vit_tokens(const bf16_t* patch, const float* cls, const float* pos, int B, int NP, int C, bf16_t* y, void* stream) {
     if (B <= 0 || NP <= 0 || (C % 2)) return SVLA_EINVAL;
     long blocks = ((long)B * (NP + 1) * (C / 2) + 255) / 256; if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(vit_tokens_kernel, dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, patch, cls, pos, B, NP, C, y);
-    return svla_launch_status();
+    return svla_launch<vit_tokens_kernel>(dim3((int)blocks), dim3(256), 0, (hipStream_t)stream, patch, cls, pos, B, NP, C, y);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -778,15 +764,13 @@ extern "C" int svla_acting_stage(const void* tok_src, void* tok_dst, long tok_by
     a.pa_src = pa_src; a.pa_dst = pa_dst; a.mask_src = mask_src; a.mask_dst = mask_dst; a.hand_src = hand_src; a.hand_dst = hand_dst; a.ts_src = ts_src; a.ts_dst = ts_dst;
     a.ids_src = ids_src; a.ids_dst = ids_dst; a.am_dst = am_dst; a.am8_dst = am8_dst; a.kvalid_dst = kvalid_dst; a.t_dev = t_dev;
     a.B = B; a.L = L; a.max_steps = max_steps; a.t = t; a.seed[0] = seed0; a.seed[1] = seed1; a.seed[2] = seed2; a.seed_inc = seed_inc;
-    hipLaunchKernelGGL(acting_stage_kernel, dim3(a.nb_tok + B), dim3(256), 0, (hipStream_t)stream, a);
-    return svla_launch_status();
+    return svla_launch<acting_stage_kernel>(dim3(a.nb_tok + B), dim3(256), 0, (hipStream_t)stream, a);
 }
 
 // ---- tower-grouped launches (csrc/launch.h; include/svla.h: svla_group_begin) -----------------------------------------------------------
-static thread_local GroupCapture* t_group_open = nullptr;      // this thread's open capture
-static thread_local GroupCapture* t_group_store = nullptr;     // allocated once per thread (~13 KiB of argument blocks)
-GroupCapture* svla_group_capture() { return t_group_open; }
-int svla_group_size() { return t_group_open ? t_group_open->size : 1; }
+static thread_local GroupState t_group;      // this thread's capture: the logic is csrc/launch_group.h, the entry points below only name the thread's state
+GroupCapture* svla_group_capture() { return t_group.open; }
+int svla_group_size() { return t_group.open ? t_group.open->size : 1; }
 // compute units of the current device, asked once per process (a failed query is not remembered).  A plain attribute query: legal inside a stream capture
 int svla_cu_count() {
     static std::atomic<int> n_cu{0};
@@ -794,68 +778,14 @@ int svla_cu_count() {
     if (!n && hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess) n_cu.store(n, std::memory_order_relaxed);
     return n;
 }
-extern "C" int svla_group_begin(int members) {
-    if (t_group_open || members < 1 || members > SVLA_MAXG) return SVLA_EINVAL;
-    if (!t_group_store) t_group_store = new GroupCapture();
-    GroupCapture* gc = t_group_store;
-    gc->size = members;
-    gc->member = 0;
-    gc->overflow = 0;
-    for (int m = 0; m < SVLA_MAXG; ++m) gc->n[m] = 0;
-    t_group_open = gc;
-    return SVLA_OK;
-}
-extern "C" int svla_group_member(int member) {
-    GroupCapture* gc = t_group_open;
-    if (!gc || member < 0 || member >= gc->size) return SVLA_EINVAL;
-    gc->member = member;
-    return SVLA_OK;
-}
-static bool group_same_launch(const DeferredLaunch& a, const DeferredLaunch& b) {
-    return a.flush == b.flush && a.smem == b.smem && a.grid.x == b.grid.x && a.grid.y == b.grid.y && a.grid.z == 1 && b.grid.z == 1 &&
-           a.block.x == b.block.x && a.block.y == b.block.y && a.block.z == b.block.z;
-}
-extern "C" int svla_group_end(void* stream) {
-    GroupCapture* gc = t_group_open;
-    if (!gc) return SVLA_EINVAL;
-    t_group_open = nullptr;                      // the launches below are real
-    hipStream_t st = (hipStream_t)stream;
-    bool lockstep = !gc->overflow;
-    for (int m = 1; m < gc->size; ++m) lockstep = lockstep && gc->n[m] == gc->n[0];
-    int rc = SVLA_OK;
-    if (lockstep) {
-        for (int j = 0; j < gc->n[0] && rc == SVLA_OK; ++j) {
-            const DeferredLaunch* ms[SVLA_MAXG];
-            bool same = gc->size > 1;
-            for (int m = 0; m < gc->size; ++m) {
-                ms[m] = &gc->q[m][j];
-                same = same && group_same_launch(gc->q[0][j], gc->q[m][j]);
-            }
-            if (same) { rc = ms[0]->flush(ms, gc->size, st); gc->grouped += 1; }
-            else for (int m = 0; m < gc->size && rc == SVLA_OK; ++m) { rc = ms[m]->flush(&ms[m], 1, st); gc->single += 1; }
-        }
-    } else {        // the members did not issue the same number of launches (e.g. one of them has a ragged row tail): member by member, in call order
-        for (int m = 0; m < gc->size && rc == SVLA_OK; ++m)
-            for (int j = 0; j < gc->n[m] && rc == SVLA_OK; ++j) {
-                const DeferredLaunch* one = &gc->q[m][j];
-                rc = one->flush(&one, 1, st);
-                gc->single += 1;
-            }
-    }
-    return rc;
-}
-extern "C" int svla_group_stats(long* grouped, long* single) {
-    GroupCapture* gc = t_group_store;
-    if (grouped) *grouped = gc ? gc->grouped : 0;
-    if (single) *single = gc ? gc->single : 0;
-    if (gc) gc->grouped = gc->single = 0;
-    return SVLA_OK;
-}
+extern "C" int svla_group_begin(int members) { return group_begin(t_group, members); }
+extern "C" int svla_group_member(int member) { return group_member(t_group, member); }
+extern "C" int svla_group_end(void* stream) { return group_end(t_group, stream); }
+extern "C" int svla_group_stats(long* grouped, long* single) { return group_stats(t_group, grouped, single); }
 
 // Zero a device buffer on the launch stream (gradient scratch that the text / embedding backward kernels accumulate into with atomics);
 // a C-ABI entry so that it is part of a recorded launch sequence instead of a framework-side fill.
 extern "C" int svla_zero_bytes(void* p, long bytes, void* stream) {
     if (!p || bytes <= 0) return SVLA_EINVAL;
-    HIP_CHECK_RET(hipMemsetAsync(p, 0, (size_t)bytes, (hipStream_t)stream));
-    return SVLA_OK;
+    return svla_memset_async(p, 0, (size_t)bytes, (hipStream_t)stream);
 }

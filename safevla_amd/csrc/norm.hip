@@ -246,12 +246,11 @@ static int norm_bwd_launch(const T* dy, int dyG, int dyGS, int dyOFF, const T* x
     if (dtok && (long)(dyG > 0 ? dyG : rows) > 2L * tok_group) return SVLA_EINVAL;
     RowMap dym{dyG, dyGS, dyOFF}, xm{xG, xGS, xOFF}, dxm{dxG, dxGS, dxOFF};
     const int blocks = norm_grid(rows, 4096);   // measured (tools/norm_bw.py, 2.97 M rows): 5.09 TB/s at 1 024 workgroups, 5.23 at 4 096 (each ends with up to 4*D atomics)
-#define NORM_BWD_CASE(DD) hipLaunchKernelGGL((norm_bwd_kernel<T, DD>), dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, dym, x, xm, gamma, beta, mean, \
+#define NORM_BWD_CASE(DD) return svla_launch<norm_bwd_kernel<T, DD>>(dim3(blocks), dim3(256), 0, (hipStream_t)stream, dy, dym, x, xm, gamma, beta, mean, \
                        rstd, rows, rms, relu, tok_group > 0 ? tok_group : 1, dres, dx, dxm, dgamma, dbeta, dtok, dx_drop, drop_cfg(drop), g_svla_det)
     if (D == 512) NORM_BWD_CASE(512);       // the policy
-    else NORM_BWD_CASE(768);                // the 768-wide imitation-learning presets (early_fusion_tsfm_models.py:275-294)
+    NORM_BWD_CASE(768);                     // the 768-wide imitation-learning presets (early_fusion_tsfm_models.py:275-294)
 #undef NORM_BWD_CASE
-    return svla_launch_status();
 }
 
 extern "C" int svla_norm_fwd_bf16(const bf16_t* x, int xG, int xGS, int xOFF, const float* gamma, const float* beta, float eps,

@@ -183,7 +183,6 @@ extern "C" int svla_resize_bicubic_aa_u8(const unsigned char* x, unsigned char* 
     }
     const long long tiles = (long long)((OH + G.TR - 1) / G.TR) * ((OW + G.TC - 1) / G.TC);
     if (tiles >= (1ll << 31)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(resize_bicubic_aa_u8_kernel, dim3((unsigned)tiles, B), dim3(RSZ_T), rsz_lds_bytes(G), (hipStream_t)stream, x, y, G, x,
+    return svla_launch<resize_bicubic_aa_u8_kernel>(dim3((unsigned)tiles, B), dim3(RSZ_T), rsz_lds_bytes(G), (hipStream_t)stream, x, y, G, x,
                        x + (size_t)B * H * W * 3);
-    return svla_launch_status();
 }

@@ -54,10 +54,9 @@ extern "C" int svla_gae_scan_f32(const float* rewards, const float* costs, const
                                  int T, int B, float* ret, float* adv, float* c_ret, float* c_adv, void* stream) {
     if (T <= 0 || B <= 0) return SVLA_EINVAL;
     const int threads = 64;
-    hipLaunchKernelGGL(gae_scan_kernel<8>, dim3((B + threads - 1) / threads), dim3(threads), 0, (hipStream_t)stream,
+    return svla_launch<gae_scan_kernel<8>>(dim3((B + threads - 1) / threads), dim3(threads), 0, (hipStream_t)stream,
                        rewards, costs, values, c_values, masks, next_v, next_cv, (float)gamma, (float)(gamma * tau), T, B,
                        ret, adv, c_ret, c_adv);
-    return svla_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -149,10 +148,9 @@ extern "C" int svla_ppo_lag_loss_fwd_bwd_f32(const float* logits, const float* v
     if (rows <= 0 || A <= 0 || A > 32) return SVLA_EINVAL;
     if (use_clipped_value && !old_values) return SVLA_EINVAL;
     const int threads = 128;
-    hipLaunchKernelGGL(ppo_lag_loss_kernel<32>, dim3((rows + threads - 1) / threads), dim3(threads), 0,
+    return svla_launch<ppo_lag_loss_kernel<32>>(dim3((rows + threads - 1) / threads), dim3(threads), 0,
                        (hipStream_t)stream, logits, values, actions, old_logp, adv, c_adv, returns, old_values, rows, A, lam,
                        clip, value_coef, action_w, ent_coef, use_clipped_value, inv_n, dlogits, dvalues, sums);
-    return svla_launch_status();
 }
 
 // PPOValue / SafePPOValue [3P]: 0.5*mean((returns - values)^2); sums[0] += sum sq err; dvalues = coef*(v-ret)*inv_n.
@@ -185,9 +183,8 @@ __global__ void value_mse_kernel(const float* __restrict__ values, const float* 
 extern "C" int svla_value_mse_fwd_bwd_f32(const float* values, const float* returns, const float* old_values, float clip, int rows,
                                           float coef, float inv_n, float* dvalues, double* sums, void* stream) {
     if (rows <= 0) return SVLA_EINVAL;
-    hipLaunchKernelGGL(value_mse_kernel, dim3((rows + 127) / 128), dim3(128), 0, (hipStream_t)stream, values, returns, old_values, clip,
+    return svla_launch<value_mse_kernel>(dim3((rows + 127) / 128), dim3(128), 0, (hipStream_t)stream, values, returns, old_values, clip,
                        rows, coef, inv_n, dvalues, sums);
-    return svla_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -274,9 +271,8 @@ extern "C" int svla_hlgauss_fwd_bwd_f32(const float* logits, const float* target
                                         float vmax, float sigma, float coef, float inv_n, float* values_out, float* dlogits, double* sums,
                                         void* stream) {
     if (rows <= 0 || NB <= 0 || NB > 256 || !(vmax > vmin) || !(sigma > 0.f)) return SVLA_EINVAL;
-    hipLaunchKernelGGL(hlgauss_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, target, dvalue, rows, NB, vmin,
+    return svla_launch<hlgauss_kernel>(dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream, logits, target, dvalue, rows, NB, vmin,
                        vmax, sigma, coef, inv_n, values_out, dlogits, sums);
-    return svla_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -312,9 +308,8 @@ __global__ void ce_loss_kernel(const float* __restrict__ logits, const long* __r
 extern "C" int svla_ce_loss_fwd_bwd_f32(const float* logits, const long* target, int rows, int A, long ignore_index,
                                         const float* n_valid, float* dlogits, double* sums, void* stream) {
     if (rows <= 0 || A <= 0 || A > 1024 || !n_valid) return SVLA_EINVAL;
-    hipLaunchKernelGGL(ce_loss_kernel, dim3((rows + 127) / 128), dim3(128), 0, (hipStream_t)stream, logits, target, rows, A,
+    return svla_launch<ce_loss_kernel>(dim3((rows + 127) / 128), dim3(128), 0, (hipStream_t)stream, logits, target, rows, A,
                        ignore_index, n_valid, dlogits, sums);
-    return svla_launch_status();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -426,10 +421,6 @@ extern "C" int svla_small_linear_bwd_f32(const float* x, const float* W, const f
     if (blocks > 256) blocks = 256;
     const dim3 grid(blocks, (D + 511) / 512);
     if (N <= 1)
-        hipLaunchKernelGGL(small_linear_bwd_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, x, W, dout, rows, N, D,
-                           T, B, accumulate_dx, dx, dW, db, g_svla_det);
-    else
-        hipLaunchKernelGGL(small_linear_bwd_kernel<20>, grid, dim3(256), 0, (hipStream_t)stream, x, W, dout, rows,
-                           N, D, T, B, accumulate_dx, dx, dW, db, g_svla_det);
-    return svla_launch_status();
+        return svla_launch<small_linear_bwd_kernel<1>>(grid, dim3(256), 0, (hipStream_t)stream, x, W, dout, rows, N, D, T, B, accumulate_dx, dx, dW, db, g_svla_det);
+    return svla_launch<small_linear_bwd_kernel<20>>(grid, dim3(256), 0, (hipStream_t)stream, x, W, dout, rows, N, D, T, B, accumulate_dx, dx, dW, db, g_svla_det);
 }

@@ -58,6 +58,15 @@ def test_product_does_not_import_oracle():
                 assert not re.search(r"^\s*(from|import)\s+oracle\b", s, flags=re.M), f
 
 
+def test_one_launch_path_in_csrc():
+    """every kernel launch of csrc/ goes through csrc/launch.h (svla_launch / the deferral sites), where a launch-group capture keeps a member's launches in order:
+    no other file launches on its own"""
+    csrc = os.path.join(ROOT, "safevla_amd", "csrc")
+    files = [f for f in sorted(os.listdir(csrc)) if os.path.isfile(os.path.join(csrc, f))]
+    assert "launch.h" in files and len(files) > 10
+    assert [f for f in files if "hipLaunchKernelGGL" in open(os.path.join(csrc, f), errors="replace").read()] == ["launch.h"]
+
+
 def test_launch_group_capture_protocol_without_a_gpu(built_lib):
     """svla_group_begin / _member / _end / _stats (tower-grouped launches, csrc/launch.h) are host logic: the protocol -- one capture per thread, members in range,
     an empty capture issues nothing -- holds without a GPU; so do the argument checks of svla_det_set_grid and svla_acting_stage (refused before any launch)."""

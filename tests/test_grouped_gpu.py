@@ -250,3 +250,109 @@ def test_grouped_launches_random_shapes_and_flavours():
                 assert torch.equal(gn[m], wn[m]), (case, "norm", M)
     from safevla_amd import _lib
     assert _lib.lib().cdll.svla_group_end(None) != 0          # no capture left open
+
+
+def _norm_inputs(seed, rows, D=512):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    x = [torch.randn(rows, D, device=DEV, generator=g).to(BF16) for _ in range(3)]
+    gam = [torch.rand(D, device=DEV, generator=g) + 0.5 for _ in range(3)]
+    bet = [torch.randn(D, device=DEV, generator=g) for _ in range(3)]
+    return g, x, gam, bet
+
+
+def test_dependent_calls_of_a_member_keep_their_order():
+    """Per member a LayerNorm (deferred: it has a grouped twin) into a zero-filled y, then rows_add(acc, y) (no twin: issued at once).  The norm is issued ahead of the
+    rows_add that reads its output -- singly, so (0, 3) -- and acc equals the two calls made outside a capture, bit for bit."""
+    _need_gpu()
+    from safevla_amd import ops
+
+    rows, D = 64, 512
+    g, x, gam, bet = _norm_inputs(21, rows)
+    acc0 = [torch.randn(rows, D, device=DEV, generator=g).to(BF16) for _ in range(3)]
+
+    def run(m, acc, y):
+        ops.norm_fwd(x[m], gam[m], bet[m], 1e-5, rows, D=D, y=y)
+        ops.rows_add(acc, D, y, D, rows)
+        return acc
+
+    zeros = lambda: [torch.zeros(rows, D, device=DEV, dtype=BF16) for _ in range(3)]
+    yw, yg = zeros(), zeros()
+    want = [run(m, acc0[m].clone(), yw[m]) for m in range(3)]
+    torch.cuda.synchronize()
+    ops.group_stats()
+    got = _grouped(lambda m: run(m, acc0[m].clone(), yg[m]))
+    torch.cuda.synchronize()
+    assert ops.group_stats() == (0, 3)
+    for m in range(3):
+        assert torch.equal(got[m], want[m]), m
+        assert not torch.equal(got[m], acc0[m])
+
+
+def test_more_launches_than_a_member_queue_holds():
+    """nine chained LayerNorms per member (SVLA_MAXQ = 8 pending launches): each reads the previous one's preallocated output; the last output equals the chain
+    outside a capture bit for bit, and all 27 launches were issued"""
+    _need_gpu()
+    from safevla_amd import ops
+
+    rows, D, n = 64, 512, 9
+    _, x, gam, bet = _norm_inputs(22, rows)
+
+    def chain(m, bufs):      # bufs: allocated by the caller, alive until the capture has ended (a deferred launch holds raw pointers)
+        for j in range(n):
+            ops.norm_fwd(x[m] if j == 0 else bufs[j - 1], gam[m], bet[m], 1e-5, rows, D=D, y=bufs[j])
+        return bufs[n - 1]
+
+    alloc = lambda: [[torch.zeros(rows, D, device=DEV, dtype=BF16) for _ in range(n)] for _ in range(3)]
+    bw, bg = alloc(), alloc()
+    want = [chain(m, bw[m]) for m in range(3)]
+    torch.cuda.synchronize()
+    ops.group_stats()
+    got = _grouped(lambda m: chain(m, bg[m]))
+    torch.cuda.synchronize()
+    grouped, single = ops.group_stats()
+    assert 3 * grouped + single == 3 * n, (grouped, single)
+    for m in range(3):
+        assert torch.equal(got[m], want[m]), m
+
+
+def test_a_capture_has_one_stream():
+    """a launch site that names another stream than the capture's first launch is refused; a capture ended on another stream issues nothing; the next capture works"""
+    _need_gpu()
+    from safevla_amd import _lib, ops
+
+    L = _lib.lib()
+    rows, D = 8, 512
+    _, x, gam, bet = _norm_inputs(23, rows)
+    other = torch.cuda.Stream()
+    norm = lambda m, y=None: ops.norm_fwd(x[m], gam[m], bet[m], 1e-5, rows, D=D, y=y)[0]
+    want = [norm(m) for m in range(3)]
+    torch.cuda.synchronize()
+    main = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+    ys = [torch.zeros(rows, D, device=DEV, dtype=BF16) for _ in range(2)]
+    L.call("svla_group_begin", 3)
+    try:
+        norm(0, ys[0])
+        with torch.cuda.stream(other):
+            with pytest.raises(_lib.SvlaError):
+                norm(0, ys[1])
+    finally:
+        assert L.cdll.svla_group_end(main) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(ys[0], want[0]) and not ys[1].any()      # the refused call neither launched nor deferred
+
+    sentinel = torch.full((rows, D), 7.0, device=DEV, dtype=BF16)
+    y = sentinel.clone()
+    L.call("svla_group_begin", 3)
+    try:
+        norm(0, y)
+    finally:
+        rc = L.cdll.svla_group_end(ctypes.c_void_p(other.cuda_stream))
+    assert rc != 0
+    torch.cuda.synchronize()
+    assert torch.equal(y, sentinel)
+
+    got = _grouped(norm)
+    torch.cuda.synchronize()
+    for m in range(3):
+        assert torch.equal(got[m], want[m]), m
